@@ -13,7 +13,12 @@ child, launched before this process touches the GPU) and passes rank 0's line
 through.  --preset c2/c3/c4/c5 selects BASELINE.json configs[1..4] (c4 =
 the headline network at 5 scenes per GPU).
 
-Also reported: roofline of the dominant kernel family (msp_conv_tile /
+A plain run sets up, warms up, times the steps and prints the result line.
+--dump-outputs DIR also writes what the last timed step computed (loss, logits,
+a fixed sample of the parameter gradients) as DIR/<name>.npy; with the same
+arguments the inputs, and so these arrays, are the same from run to run.
+
+Reported with --full only (extra untimed runs after the timed steps): roofline of the dominant kernel family (msp_conv_tile /
 msp_conv_nbr: bf16 MFMA on exact three-piece splits -- six bf16 products per
 fp32 multiply-add -- so the peak is 2500/6 TF/s fp32-equivalent; a call on the
 f32-MFMA forms would be priced at 157.3 and the peak reported is the
@@ -238,6 +243,27 @@ def cpu_baseline(args, batch, iters=3):
                       f"({', '.join(f'{t:.2f}' for t in times)} s)"}
 
 
+DUMP_SAMPLE = 1 << 20  # --dump-outputs: entries kept of the flattened gradients and parameters (4 MB each)
+
+
+def dump_outputs(path, out, model):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files -- its loss and logits,
+    and the same fixed (seeded) sample of the parameters' gradients and of the parameters after the step's
+    update, both flattened in model.parameters() order."""
+    os.makedirs(path, exist_ok=True)
+    loss, logits = out
+    params = list(model.parameters())
+    flat = {"grad_sample": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1)
+                                      for p in params]),
+            "param_sample": torch.cat([p.detach().reshape(-1) for p in params])}
+    n = flat["param_sample"].numel()
+    if n > DUMP_SAMPLE:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).integers(0, n, DUMP_SAMPLE))).to(loss.device)
+        flat = {k: v[idx] for k, v in flat.items()}
+    for name, t in dict(loss=loss, logits=logits, **flat).items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def balanced_batch(args, rank, world, k):
     """Batch k of this rank under LPT assignment: the same pool of world x batch procedural rooms on every rank
     (seeded by k), sharded by point count with wsss3d.dp.balanced_shards, then this rank's rooms through the
@@ -269,6 +295,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the per-family and "
+                         "step-level rooflines (--record, --family-steps), the per-level statistics and multiply-add "
+                         "count, and the CPU baseline (--no-cpu, --cpu-iters).  Off: those options have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32): loss, logits, and "
+                         "grad_sample = a fixed seeded sample of the flattened parameter gradients")
     ap.add_argument("--preset", choices=sorted(PRESETS), default=None,
                     help="BASELINE.json configs[1..4]: c2 UNet m16 r1 VGG b4, c3 (default) UNet m32 r2 residual b8, "
                          "c4 the same at 5 scenes per GPU, c5 MultiLabelContrastive FCNet m32 + text")
@@ -277,15 +310,15 @@ def main():
     ap.add_argument("--m", type=int, default=None)
     ap.add_argument("--reps", type=int, default=None)
     ap.add_argument("--residual", type=int, default=None)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--cpu-iters", type=int, default=3, help="timed cpu_baseline iterations (median)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--cpu-iters", type=int, default=3, help="--full: timed cpu_baseline iterations (median)")
     ap.add_argument("--record", choices=["all", "conv", "none"], default="conv",
-                    help="HIP-event bracketing of the recorded calls in the timed steps (roofline): the conv "
+                    help="--full: HIP-event bracketing of the recorded calls in the timed steps (roofline): the conv "
                          "family only (default), every recorded family, or none.  Every bracketed call costs "
                          "about 2.5 us of stream time (all families: ~3 ms per step), so the other families' "
                          "rooflines come from --family-steps extra recorded steps after the timed region")
     ap.add_argument("--family-steps", type=int, default=5,
-                    help="untimed steps after the timed region with every family recorded (per-family rooflines "
+                    help="--full: untimed steps after the timed region with every family recorded (per-family rooflines "
                          "and the step-level compulsory bytes); 0 = none")
     ap.add_argument("--foreach-adam", action="store_true", help="torch's foreach Adam instead of the fused one")
     ap.add_argument("--adam", choices=["library", "torch"], default="library",
@@ -500,7 +533,7 @@ def main():
             prefetch(i)
         if host_t is not None:
             host_t.append((h1 - h0, h2 - h1, h3 - h2, time.perf_counter() - h3))
-        return loss
+        return loss, logits
 
     from sparseconvnet import metadata as scn_meta
     cur = torch.cuda.current_stream(dev)
@@ -510,6 +543,8 @@ def main():
     # device-synchronising free each step
     graph_pool = torch.cuda.graph_pool_handle() if use_graph else None
 
+    step_out = {}  # graph mode: step index -> (loss, logits) of its captured graph, until the step is replayed
+    last_out = None  # (loss, logits) of the last timed step (--dump-outputs)
     capture_s = []
     capture_parts = []  # BENCH_HOST_TIMING: (capture_begin, body, capture_end) host seconds
 
@@ -529,7 +564,7 @@ def main():
             opt.step()
         elif gsync.overlap:
             gsync.join()  # the exchange's graph nodes rejoin the captured stream
-        return loss
+        return loss, logits
 
     def _hip_runtime():
         # the HIP runtime torch itself loaded (by soname); only --graph-upload calls into it
@@ -558,7 +593,7 @@ def main():
             g.capture_begin(pool=graph_pool, capture_error_mode="relaxed")
             c1 = time.perf_counter()
             try:
-                body(i)
+                step_out[i] = body(i)  # the graph's output tensors: they hold step i's values after its replay
             except BaseException:
                 # end the capture and discard the graph before the error propagates (an open capture makes
                 # ~CUDAGraph terminate the process); sparseconvnet.graphs.capture is the same path
@@ -617,8 +652,9 @@ def main():
 
     for i in range(args.warmup):
         step(i)
-    rec = KernelRecorder(args.record if not use_graph else "none", pool=2 * 700 * args.steps)
-    _lib.set_recorder(rec if args.record != "none" and not use_graph else None)
+    rec_mode = args.record if args.full and not use_graph else "none"
+    rec = KernelRecorder(rec_mode, pool=2 * 700 * args.steps)
+    _lib.set_recorder(rec if rec_mode != "none" else None)
     entry = None
     worker, fut = None, None
     if use_graph and args.prefetch_thread:
@@ -649,6 +685,7 @@ def main():
         for i in range(args.steps):
             h0 = time.perf_counter()
             done = replay(entry)
+            last_out = step_out.pop(i)
             bounds.append(done)
             inflight.append((entry, done, i))
             h1 = time.perf_counter()
@@ -761,7 +798,7 @@ def main():
             worker.shutdown()
     else:
         for i in range(args.steps):
-            step(i)
+            last_out = step(i)
             bounds.append(torch.cuda.Event(enable_timing=True))
             bounds[-1].record(cur)
     torch.cuda.synchronize()
@@ -776,6 +813,8 @@ def main():
         print(out.getvalue(), file=sys.stderr)
     step_ms = [a.elapsed_time(b) for a, b in zip(bounds[:-1], bounds[1:])]
     rec.active = False
+    if args.dump_outputs and rank == 0:  # before anything else runs a step or releases the last step's graph
+        dump_outputs(args.dump_outputs, last_out, model)
     held.clear()  # every step has completed
     if use_graph:
         inflight = entry = None
@@ -793,7 +832,7 @@ def main():
     rank_host = [dp.gather_floats(v) for v in loop_med] if world > 1 else [[v] for v in loop_med]
     _lib.set_recorder(None)
     fams = rec.summary()
-    fam_steps = args.family_steps if (args.record != "all" or use_graph) else 0
+    fam_steps = args.family_steps if args.full and (args.record != "all" or use_graph) else 0
     if fam_steps:
         # every family bracketed, outside the timed region (see --record)
         rec_all = KernelRecorder("all", pool=2 * 700 * fam_steps)
@@ -810,18 +849,20 @@ def main():
         fams_all = fams
         fam_steps = args.steps
 
-    # one untimed forward for the per-level statistics and the MAC counter
-    scn.forward_pass_multiplyAdd_count = 0
-    inner = getattr(model, "module", model)
-    x0 = batches[0][0]
-    enc = inner.pc_encoder.encoder
-    with torch.no_grad():
-        t_in = enc[0]([x0.coords, x0.feature])
-        t_out = t_in
-        for mod in list(enc)[1:-1]:
-            t_out = mod(t_out)
-    stats = level_stats(t_in.metadata)
-    macs = scn.forward_pass_multiplyAdd_count
+    stats = macs = None
+    if args.full:
+        # one untimed forward for the per-level statistics and the MAC counter
+        scn.forward_pass_multiplyAdd_count = 0
+        inner = getattr(model, "module", model)
+        x0 = batches[0][0]
+        enc = inner.pc_encoder.encoder
+        with torch.no_grad():
+            t_in = enc[0]([x0.coords, x0.feature])
+            t_out = t_in
+            for mod in list(enc)[1:-1]:
+                t_out = mod(t_out)
+        stats = level_stats(t_in.metadata)
+        macs = scn.forward_pass_multiplyAdd_count
 
     if rank == 0:
         ms_step = dt_max / args.steps * 1e3
@@ -952,7 +993,7 @@ def main():
                         "arithmetic's native rate), x6 peak = 2500/6 TF/s (the split-bf16 path the convolutions "
                         "take); frac = t_roof / measured ms_per_step",
             }
-        if world == 1 and not args.no_cpu and not contrastive:
+        if args.full and world == 1 and not args.no_cpu and not contrastive:
             res["cpu_baseline"] = cpu_baseline(args, host_batches[0], args.cpu_iters)
         print(json.dumps(res), flush=True)
     if dist.is_initialized():

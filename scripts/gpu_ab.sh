@@ -8,6 +8,8 @@
 set -o pipefail
 TAG=${TAG:-ab}
 ROUNDS=${ROUNDS:-2}
+# --full: the family ms/step printed below come from bench.py's recorded steps
+BENCH_ARGS=${BENCH_ARGS:---steps 15 --warmup 5 --full}
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 EXP=${EXP_LIB:-$GRAFT_REPO_ROOT/3d-weakly-supervised-semantic-segmentation_amd/lib/libmi3dsparse_exp.so}

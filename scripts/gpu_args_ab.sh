@@ -4,6 +4,8 @@
 set -o pipefail
 TAG=${TAG:-args}
 ROUNDS=${ROUNDS:-2}
+# --full: the family ms/step printed below come from bench.py's recorded steps
+BENCH_ARGS=${BENCH_ARGS:---steps 15 --warmup 5 --full}
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 : > gpurun_out/args_$TAG.log

@@ -5,7 +5,7 @@
 #
 #   smoke    __graft_entry__.smoke()
 #   test     the GPU suite (PYTEST_K selects tests, PYTEST_FILES the files; default: all of tests/ -m gpu)
-#   bench    bench.py (BENCH_ARGS, default --gpus 1 --steps 20 --warmup 5)
+#   bench    bench.py (BENCH_ARGS, default --gpus 1 --steps 20 --warmup 5 --full: rooflines and CPU baseline included)
 #   prof     rocprofv3 kernel trace + stats of the bench (scripts/gpu_profile.sh)
 #   traffic  PMC FETCH_SIZE / WRITE_SIZE of the conv family (scripts/pmc_traffic.sh)
 #   pmc      per-kernel PMC summary (scripts/gpu_pmc.sh)
@@ -29,7 +29,7 @@ for st in ${STEPS//,/ }; do
     test) timeout -k 10 1100 python -u -m pytest ${PYTEST_FILES:-tests} -m gpu -x -v -s --timeout 900 \
             --timeout-method thread ${PYTEST_K:+-k "$PYTEST_K"} > $log 2>&1; rc=$?
           tail -3 $log ;;
-    bench) timeout -k 10 400 python -u bench.py ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5} > $log 2>&1; rc=$?
+    bench) timeout -k 10 400 python -u bench.py ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5 --full} > $log 2>&1; rc=$?
            tail -1 $log | cut -c1-700 ;;
     prof) TAG=$TAG bash scripts/gpu_profile.sh > $log 2>&1; rc=$?; head -45 $log ;;
     traffic) TAG=$TAG bash scripts/pmc_traffic.sh > $log 2>&1; rc=$?; tail -5 $log ;;

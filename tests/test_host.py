@@ -172,33 +172,30 @@ def test_balanced_shards():
     assert abs(loads[0] - loads[1]) <= 20
 
 
-REF = "/root/reference"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
 def test_reference_model_file_runs_on_this_package():
-    """Drop-in check: the reference's models/SparseConvNet.py, loaded unmodified
-    with THIS package as `sparseconvnet`, registers its encoders and builds
-    module trees identical (keys, shapes, seeded values) to wsss3d's."""
-    import importlib.util
-    import sys
-    import types
-    sys.modules["easydict"] = types.SimpleNamespace(EasyDict=EasyDict)
-    if REF not in sys.path:
-        sys.path.append(REF)
-    spec = importlib.util.spec_from_file_location("ref_models_on_mi3dsparse", os.path.join(REF, "models", "SparseConvNet.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    assert mod.scn is scn
-    for name, m, reps, res in [("SparseConvUNet", 32, 2, True), ("SparseConvFCNet", 16, 1, False),
-                               ("SparseConvFCNetDirectUpPoolLight", 16, 1, True)]:
-        torch.manual_seed(5)
-        ref_enc = getattr(mod, name)(name, m=m, dimension=3, full_scale=4096, block_reps=reps, residual_blocks=res)
-        torch.manual_seed(5)
-        ours = MODEL_REGISTRY.get(name)[0](name, m=m, dimension=3, full_scale=4096, block_reps=reps,
-                                           residual_blocks=res)
-        a, b = ref_enc.state_dict(), ours.state_dict()
-        assert list(a) == list(b) and all(torch.equal(a[k], b[k]) for k in a), name
+    """Drop-in check, from a recorded run (tests/golden/make_dropin_golden.py -> dropin_state.json): the
+    reference's models/SparseConvNet.py, loaded unmodified with THIS package as `sparseconvnet`, registered its
+    encoders and built module trees at a fixed seed.  Every name that file takes from the `sparseconvnet`
+    namespace must exist here, and wsss3d's encoders built at the same seed must be identical to the recorded
+    trees: keys, shapes, and the seeded values (leading entries, sum and sum of magnitudes of every tensor)."""
+    want = json.load(open(os.path.join(GOLD, "dropin_state.json")))
+    assert want["scn_names"] and all(hasattr(scn, n) for n in want["scn_names"])
+    assert len(want["encoders"]) == 3
+    for key, entries in want["encoders"].items():
+        name, m, reps, res = key.split("-")
+        torch.manual_seed(want["seed"])
+        ours = MODEL_REGISTRY.get(name)[0](name, m=int(m[1:]), dimension=3, full_scale=4096, block_reps=int(reps[1:]),
+                                           residual_blocks=bool(int(res)))
+        got = ours.state_dict()
+        assert list(got) == [e[0] for e in entries], key
+        for k, shape, head, total, mag in entries:
+            v = got[k].double()
+            assert list(v.shape) == shape, (key, k)
+            # the recorded numbers are these tensors' own fp32 values and fp64 sums of them: equal up to the
+            # last-bit differences between CPUs' vectorised random fills
+            np.testing.assert_allclose(v.reshape(-1)[:want["head"]].numpy(), head, rtol=1e-6, atol=1e-9, err_msg=k)
+            np.testing.assert_allclose(v.sum().item(), total, rtol=1e-6, atol=1e-6 * mag + 1e-9, err_msg=k)
+            np.testing.assert_allclose(v.abs().sum().item(), mag, rtol=1e-6, atol=1e-9, err_msg=k)
 
 
 def test_scene_ranges_match_host_logic():
@@ -226,3 +223,31 @@ def test_bench_presets_and_host_cores():
     assert 1 <= cores <= (os.cpu_count() or cores) and info["cpu_model"]
     assert bench.family("subm_fwd/x6g") == "conv" and bench.family("wgrad/x6") == "wgrad"
     assert bench.family("bn_fwd/hbm") == "bn" and bench.family("deconv_fwd/f32") == "pairs"
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy files of the step's loss and logits and of one fixed sample of the
+    flattened gradients and parameters (the same entries of both, the same on every call)."""
+    import bench
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(5, 7), torch.nn.Linear(7, 3), torch.nn.Linear(3, 3))
+    logits = model[1](model[0](torch.randn(4, 5)))  # model[2] takes no part: its gradients are None
+    loss = logits.square().mean()
+    loss.backward()
+    flat_p = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).numpy()
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1)
+                        for p in model.parameters()]).numpy()
+    bench.dump_outputs(str(tmp_path / "a"), (loss, logits), model)
+    a = {n[:-4]: np.load(tmp_path / "a" / n) for n in os.listdir(tmp_path / "a")}
+    assert sorted(a) == ["grad_sample", "logits", "loss", "param_sample"]
+    assert all(x.dtype == np.float32 for x in a.values())
+    assert a["loss"] == np.float32(loss.item()) and np.array_equal(a["logits"], logits.detach().numpy())
+    assert np.array_equal(a["param_sample"], flat_p) and np.array_equal(a["grad_sample"], flat_g)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 16)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), (loss, logits), model)
+    b, c = ({n: np.load(tmp_path / d / (n + ".npy")) for n in ("grad_sample", "param_sample")} for d in ("b", "c"))
+    assert b["param_sample"].shape == b["grad_sample"].shape == (16,)
+    assert all(np.array_equal(b[n], c[n]) for n in b)
+    idx = np.flatnonzero(np.isin(flat_p, b["param_sample"]))  # the sampled entries, found by their (distinct) values
+    assert set(flat_g[idx]) == set(b["grad_sample"])
