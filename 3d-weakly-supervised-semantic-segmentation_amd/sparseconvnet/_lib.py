@@ -119,6 +119,11 @@ PROTOTYPES = {
     "msp_point_rows_bias": (I, [P, I64, I, P, P, I64, P, P]),
     "msp_index_add_workspace_size": (SZ, [I64, I64]),
     "msp_index_add_rows": (I, [P, I64, I, P, P, I64, P, SZ, P]),
+    "msp_pseudo_labels": (I, [P, I64, I, P, P, I, F, P, P, P, P, P, P]),
+    "msp_confusion": (I, [P, P, I64, I, P, P]),
+    "msp_point_ce_workspace_size": (SZ, [I64]),
+    "msp_point_ce_fwd": (I, [P, I64, I, P, P, P, P, P, P, SZ, P]),
+    "msp_point_ce_bwd": (I, [P, I64, I, P, P, P, P, P, P]),
     "msp_merge_workspace_size": (SZ, [I, I64]),
     "msp_merge": (I, [P, P, P, P, I, I64, I, D, P, P, P, P, P, P, I, P, P, P, P, I64, P, P, P, SZ, P]),
 }

@@ -1121,6 +1121,101 @@ def index_add_rows(store, ids, src):
     return store
 
 
+PSEUDO_MAX_CLASSES = 64  # msp_pseudo.hip's kMaxC; the library checks it too
+
+
+def _check_labels(t, n, what):
+    if t.dtype != torch.int64 or not t.is_cuda or t.dim() != 1 or t.numel() != n:
+        raise ValueError(f"{what}: need {n} int64 labels on the device, got {tuple(t.shape)} {t.dtype} {t.device}")
+    return t.contiguous()
+
+
+def pseudo_labels(logits, scene_labels, point_offsets, threshold, gt=None, counts=None, confusion=None,
+                  want_conf=False):
+    """msp_pseudo_labels: mask / normalise / sigmoid / max / threshold of the (N, C) logits in one launch, with the
+    quality counts.  point_offsets: (B + 1,) int64 device tensor.  counts (3,) int64 {labelled, correct, rows} and
+    confusion (C, C) int64 are accumulated in place (a zeroed counts is made when None).  Returns
+    (labels, conf or None, counts).  logits is not modified; nothing is read back."""
+    _check_feats(logits)
+    if logits.dim() != 2:
+        raise ValueError(f"pseudo_labels: logits {tuple(logits.shape)}")
+    logits = logits.contiguous()
+    N, C = logits.shape
+    dev = logits.device
+    _check_feats(scene_labels)
+    scene_labels = scene_labels.contiguous()
+    B = scene_labels.size(0)
+    if scene_labels.dim() != 2 or scene_labels.size(1) != C or B < 1:
+        raise ValueError(f"pseudo_labels: scene_labels {tuple(scene_labels.shape)} for {C} classes")
+    point_offsets = _check_labels(point_offsets, B + 1, "pseudo_labels: point_offsets")
+    if gt is not None:
+        gt = _check_labels(gt, N, "pseudo_labels: gt")
+    if counts is None:
+        counts = torch.zeros(3, dtype=torch.int64, device=dev)
+    elif counts.dtype != torch.int64 or counts.numel() != 3 or not counts.is_contiguous():
+        raise ValueError("pseudo_labels: counts must be 3 contiguous int64")
+    if confusion is not None:
+        if gt is None:
+            raise ValueError("pseudo_labels: a confusion matrix needs gt")
+        if confusion.dtype != torch.int64 or tuple(confusion.shape) != (C, C) or not confusion.is_contiguous():
+            raise ValueError(f"pseudo_labels: confusion must be a contiguous int64 ({C}, {C})")
+    labels = torch.empty(N, dtype=torch.int64, device=dev)
+    conf = torch.empty(N, dtype=torch.float32, device=dev) if want_conf else None
+    call("msp_pseudo_labels", ptr(logits), N, C, ptr(scene_labels), ptr(point_offsets), B, float(threshold), ptr(gt),
+         ptr(labels), ptr(conf), ptr(counts), ptr(confusion), _stream(logits))
+    return labels, conf, counts
+
+
+def confusion_add(confusion, pred, gt):
+    """confusion[pred * C + gt] += 1 over the rows with 0 <= gt < C (utils/iou.py:19-22) on the device
+    (msp_confusion); rows whose pred is outside [0, C) are skipped.  confusion: contiguous int64 (C, C)."""
+    if confusion.dtype != torch.int64 or confusion.dim() != 2 or confusion.size(0) != confusion.size(1) \
+            or not confusion.is_contiguous():
+        raise ValueError(f"confusion_add: confusion must be a contiguous square int64 matrix")
+    pred = _check_labels(pred, pred.numel(), "confusion_add: pred")
+    gt = _check_labels(gt, pred.numel(), "confusion_add: gt")
+    call("msp_confusion", ptr(pred), ptr(gt), pred.numel(), confusion.size(0), ptr(confusion), _stream(pred))
+    return confusion
+
+
+class PointCrossEntropyFunction(torch.autograd.Function):
+    """F.cross_entropy(logits[labels != -100], labels[labels != -100]) (utils/loss.py:29-33) without the boolean
+    gather: the kept count stays on the device (msp_point_ce_fwd / _bwd), so forward and backward make no host
+    read and can be captured into a graph.  Returns (loss, n_kept, n_bad); n_bad counts the labels that are
+    neither -100 nor a class (their rows are ignored, never indexed)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        _check_feats(logits)
+        if logits.dim() != 2:
+            raise ValueError(f"PointCrossEntropy: logits {tuple(logits.shape)}")
+        logits = logits.contiguous()
+        N, C = logits.shape
+        labels = _check_labels(labels, N, "PointCrossEntropy: labels")
+        dev = logits.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        nums = torch.empty(2, dtype=torch.int64, device=dev)
+        lse = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
+        wsb = int(_lib.query("msp_point_ce_workspace_size", _lib.I64(N)))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        call("msp_point_ce_fwd", ptr(logits), N, C, ptr(labels), ptr(loss), ptr(nums), ptr(nums[1:]), ptr(lse),
+             ptr(ws), wsb, _stream(logits))
+        ctx.save_for_backward(logits, labels, lse, nums)
+        n_kept, n_bad = nums[0], nums[1]
+        ctx.mark_non_differentiable(n_kept, n_bad)
+        return loss, n_kept, n_bad
+
+    @staticmethod
+    def backward(ctx, g, _gk, _gb):
+        logits, labels, lse, nums = ctx.saved_tensors
+        N, C = logits.shape
+        g = g.to(torch.float32).contiguous()
+        dlogits = torch.empty_like(logits)
+        call("msp_point_ce_bwd", ptr(logits), N, C, ptr(labels), ptr(lse), ptr(nums), ptr(g), ptr(dlogits),
+             _stream(logits))
+        return dlogits, None
+
+
 class UnPoolingFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, rules, n_fine):

@@ -494,6 +494,45 @@ size_t msp_index_add_workspace_size(int64_t n, int64_t n_store);
 int msp_index_add_rows(float* store, int64_t n_store, int C, const int64_t* ids, const float* src, int64_t n,
                        void* ws, size_t ws_bytes, msp_stream_t stream);
 
+/* ---------------- pseudo-label stage (pseudoLabelGeneration.py:46-59, utils/stats.py:5-48, utils/iou.py:19-22,
+ * utils/loss.py:29-33).  logits are (N, C) float32 rows with 1 <= C <= 64; label vectors are int64 with -100 =
+ * unlabelled.  No entry point below reads anything back to the host, so each can be captured into a graph. */
+
+/* stats.get_pseudo_labels + assess_label_quality in one pass.  Scene b owns rows [point_offsets[b],
+ * point_offsets[b+1]) (B + 1 device int64, empty scenes allowed) and masks them with scene_labels[b][C].  Per row:
+ * m = logits * scene_labels[b]; v = m / max(||m||_2, 1e-12); conf = max_c sigmoid(v_c); label = the first c that
+ * attains it (torch's tie rule), or -100 when conf < threshold.  A masked-out class gives exactly sigmoid(0) = 0.5,
+ * so with threshold 0.5 a row whose present classes are all negative is labelled with its first absent class, as
+ * in the reference.  logits is never written (the reference multiplies it in place).  Deviation: a row with a
+ * non-finite logit gets label -100 and conf NaN and is not counted as labelled (the reference's result there is an
+ * accident of NaN comparisons); rows owned by no scene get -100 as well.
+ * labels[N]; conf[N] (may be NULL); gt[N] (may be NULL: nothing is counted as correct).  ACCUMULATED, zeroed by the
+ * caller once per pass: counts[3] += {labelled rows, labelled rows with label == gt, rows owned by a scene};
+ * confusion[C][C] (may be NULL; needs gt) [label * C + gt] += 1 over labelled rows with 0 <= gt < C.  All
+ * accumulation is in integers: the result does not depend on the execution order. */
+int msp_pseudo_labels(const float* logits, int64_t N, int C, const float* scene_labels, const int64_t* point_offsets,
+                      int B, float threshold, const int64_t* gt, int64_t* labels, float* conf, int64_t* counts,
+                      int64_t* confusion, msp_stream_t stream);
+
+/* iou.confusion_matrix on the device: confusion[C][C] (int64, ACCUMULATED) [pred * C + gt] += 1 over the rows
+ * with 0 <= gt < C; rows whose pred is outside [0, C) are skipped. */
+int msp_confusion(const int64_t* pred, const int64_t* gt, int64_t n, int C, int64_t* confusion,
+                  msp_stream_t stream);
+
+/* F.cross_entropy(logits[labels != -100], labels[labels != -100]) (utils/loss.py:29-33) without the gather.
+ * Forward: lse[i] = log sum_c exp(logits[i][c]) (row maximum subtracted) for every row; over the kept rows
+ * (0 <= labels[i] < C) loss = sum(lse[i] - logits[i][labels[i]]) / n_kept, summed in a fixed order (fp64 block
+ * partials in ws, then one block: bitwise reproducible).  Writes the device scalars loss (f32; NaN when no row is
+ * kept, as torch's mean over nothing), n_kept and n_bad (int64) = rows whose label is neither -100 nor in [0, C):
+ * such a label is never used as an index, its row is ignored.  ws_bytes >= msp_point_ce_workspace_size(N).
+ * Backward: dlogits[i][c] = gout * (exp(logits[i][c] - lse[i]) - [c == labels[i]]) / n_kept for kept rows and
+ * exactly 0 for the others; gout (f32 scalar) and n_kept are read from device memory. */
+size_t msp_point_ce_workspace_size(int64_t N);
+int msp_point_ce_fwd(const float* logits, int64_t N, int C, const int64_t* labels, float* loss, int64_t* n_kept,
+                     int64_t* n_bad, float* lse, void* ws, size_t ws_bytes, msp_stream_t stream);
+int msp_point_ce_bwd(const float* logits, int64_t N, int C, const int64_t* labels, const float* lse,
+                     const int64_t* n_kept, const float* gout, float* dlogits, msp_stream_t stream);
+
 /* ---------------- batch assembly on the device:
  * the per-point part of trainMerge (mode 0, dataset/data.py:135-238) and
  * valMerge (mode 1, :256-310) for B scenes already in HBM.  Scene b is points
