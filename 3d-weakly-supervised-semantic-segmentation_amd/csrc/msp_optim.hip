@@ -9,6 +9,11 @@
 // which a step's autograd allocates afresh, travel in the kernel arguments (<= 256 per launch: a captured graph
 // keeps them).  The step count is a device scalar bumped by a one-thread kernel first, so captured steps replay.
 //
+// msp_adam_step_dev is the form the training loop uses (train.py:39-44: Adam under a StepLR, state resumed from a
+// checkpoint): one step count per tensor, advanced only for tensors that had a gradient (torch.optim.Adam's rule),
+// and lr / betas / eps / weight_decay read from five device doubles, so a replayed graph follows whatever the host
+// last copied there.  Same grid and element update; the counts are advanced by a one-block launch after it.
+//
 // Per element, the arithmetic of torch's fused Adam (ADAM_MODE original, amsgrad off, fp32 opmath):
 //   g += wd * p;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g;
 //   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
@@ -36,13 +41,9 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
   p -= step_size * m / denom;
 }
 
-__global__ __launch_bounds__(kAdamThreads) void adam_step_kernel(const msp_adam_tensor* __restrict__ tab,
-                                                                 const int64_t* __restrict__ chunk_start, int n,
-                                                                 const AdamGrads grads,
-                                                                 const float* __restrict__ step, double lr, double b1d,
-                                                                 double b2d, float eps, float wd) {
+// the tensor that chunk (block) b belongs to: chunk_start[i] <= b < chunk_start[i + 1], one binary search per block
+__device__ __forceinline__ int adam_tensor_of(const int64_t* __restrict__ chunk_start, int n, int64_t b) {
   __shared__ int s_i;
-  const int64_t b = blockIdx.x;
   if (threadIdx.x == 0) {
     int lo = 0, hi = n;  // chunk_start[lo] <= b < chunk_start[hi]
     while (hi - lo > 1) {
@@ -53,12 +54,13 @@ __global__ __launch_bounds__(kAdamThreads) void adam_step_kernel(const msp_adam_
     s_i = lo;
   }
   __syncthreads();
-  const int i = __builtin_amdgcn_readfirstlane(s_i);
-  const float* gp = grads.g[i];
-  if (gp == nullptr) return;  // a parameter without a gradient this step: untouched
-  const msp_adam_tensor t = tab[i];
-  const int64_t e0 = (b - chunk_start[i]) * kAdamChunk;
-  const double sd = step[0];  // bias corrections once per block, in double
+  return __builtin_amdgcn_readfirstlane(s_i);
+}
+
+// one block's chunk of tensor t (elements e0 .. e0 + kAdamChunk, clipped to t.n) at step count sd
+__device__ __forceinline__ void adam_chunk(const msp_adam_tensor& t, const float* __restrict__ gp, int64_t e0,
+                                           double sd, double lr, double b1d, double b2d, float eps, float wd) {
+  // bias corrections once per block, in double
   const float step_size = (float)(lr / (1.0 - pow(b1d, sd))), bc2_sqrt = (float)sqrt(1.0 - pow(b2d, sd));
   const float b1 = (float)b1d, b2 = (float)b2d, omb1 = (float)(1.0 - b1d), omb2 = (float)(1.0 - b2d);
   const bool vec = (t.n & 3) == 0 && ((((uintptr_t)t.param) | ((uintptr_t)t.exp_avg) | ((uintptr_t)t.exp_avg_sq) |
@@ -97,6 +99,43 @@ __global__ __launch_bounds__(kAdamThreads) void adam_step_kernel(const msp_adam_
   }
 }
 
+__global__ __launch_bounds__(kAdamThreads) void adam_step_kernel(const msp_adam_tensor* __restrict__ tab,
+                                                                 const int64_t* __restrict__ chunk_start, int n,
+                                                                 const AdamGrads grads,
+                                                                 const float* __restrict__ step, double lr, double b1d,
+                                                                 double b2d, float eps, float wd) {
+  const int64_t b = blockIdx.x;
+  const int i = adam_tensor_of(chunk_start, n, b);
+  const float* gp = grads.g[i];
+  if (gp == nullptr) return;  // a parameter without a gradient this step: untouched
+  adam_chunk(tab[i], gp, (b - chunk_start[i]) * kAdamChunk, (double)step[0], lr, b1d, b2d, eps, wd);
+}
+
+// msp_adam_step_dev: the step count is per tensor and the hyper-parameters are device memory, so a captured launch
+// follows a learning-rate schedule and a tensor without a gradient keeps its count.  Every block of tensor i reads
+// steps[i] (nothing in this launch writes it) and uses t = steps[i] + 1; adam_advance_kernel, next on the stream,
+// stores t for the tensors that had a gradient.
+__global__ __launch_bounds__(kAdamThreads) void adam_step_dev_kernel(const msp_adam_tensor* __restrict__ tab,
+                                                                     const int64_t* __restrict__ chunk_start, int n,
+                                                                     const AdamGrads grads,
+                                                                     const float* __restrict__ steps,
+                                                                     const double* __restrict__ hyper) {
+  const int64_t b = blockIdx.x;
+  const int i = adam_tensor_of(chunk_start, n, b);
+  const float* gp = grads.g[i];
+  if (gp == nullptr) return;
+  adam_chunk(tab[i], gp, (b - chunk_start[i]) * kAdamChunk, (double)steps[i] + 1.0, hyper[0], hyper[1], hyper[2],
+             (float)hyper[3], (float)hyper[4]);
+}
+
+static_assert(MSP_ADAM_MAX_TENSORS <= kAdamThreads, "adam_advance_kernel: one thread per tensor, one block");
+
+__global__ __launch_bounds__(kAdamThreads) void adam_advance_kernel(float* __restrict__ steps, int n,
+                                                                    const AdamGrads grads) {
+  const int i = threadIdx.x;
+  if (i < n && grads.g[i] != nullptr) steps[i] += 1.f;
+}
+
 }  // namespace msp
 
 using namespace msp;
@@ -120,6 +159,22 @@ int msp_adam_step(const msp_adam_tensor* table, const int64_t* chunk_start, cons
                                                                  (float)eps, (float)weight_decay);
   }
   return check_launch("msp_adam_step");
+}
+
+int msp_adam_step_dev(const msp_adam_tensor* table, const int64_t* chunk_start, const float* const* grads, int n,
+                      int64_t n_chunks, float* steps, const double* hyper, msp_stream_t stream) {
+  MSP_REQUIRE(n >= 0 && n <= MSP_ADAM_MAX_TENSORS, "msp_adam_step_dev: 0 <= n <= %d tensors per call (got %d)",
+              MSP_ADAM_MAX_TENSORS, n);
+  MSP_REQUIRE(n_chunks >= 0 && (n == 0 || (table && chunk_start && grads && steps && hyper)),
+              "msp_adam_step_dev: NULL argument");
+  if (n == 0) return 0;
+  hipStream_t s = as_stream(stream);
+  AdamGrads g{};
+  for (int i = 0; i < n; ++i) g.g[i] = grads[i];
+  if (n_chunks > 0)
+    adam_step_dev_kernel<<<(unsigned)n_chunks, kAdamThreads, 0, s>>>(table, chunk_start, n, g, steps, hyper);
+  adam_advance_kernel<<<1, kAdamThreads, 0, s>>>(steps, n, g);
+  return check_launch("msp_adam_step_dev");
 }
 
 }  // extern "C"

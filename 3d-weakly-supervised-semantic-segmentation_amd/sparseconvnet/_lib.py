@@ -93,6 +93,7 @@ PROTOTYPES = {
     "msp_conv_pairs_x6": (I, [P, I, P, I, I, P, P, P, P, I64, P, P, SZ, P]),
     "msp_adam_chunks": (I64, [I64]),
     "msp_adam_step": (I, [P, P, P, I, I64, P, I, D, D, D, D, D, P]),
+    "msp_adam_step_dev": (I, [P, P, P, I, I64, P, P, P]),
     "msp_add_bn_stats": (I, [P, P, I64, I, P, P, P]),
     "msp_conv_bn_parts": (I64, [I64]),
     "msp_conv_local_bn": (I, [P, I, P, I, I, I, I, P, P, P, P, P, I64, P, P, SZ, P, P]),

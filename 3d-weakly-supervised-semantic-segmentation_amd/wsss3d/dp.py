@@ -206,6 +206,12 @@ class GradSync:
             self._next += 1
         if self._side is not None:
             torch.cuda.current_stream(self.flat.device).wait_stream(self._side)
+            if not torch.cuda.is_current_stream_capturing():
+                # an eager step (a warm-up before the captured ones): its collectives' Works leave the watchdog's
+                # list here, whoever the caller is -- a one-rank group has no barrier + settle() before its first
+                # capture, and a Work still listed when the exchange stream joins that capture ends the process
+                # (settle() below)
+                settle(self.flat.device)
         self._pending = None
 
     def abort(self):

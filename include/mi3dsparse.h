@@ -574,6 +574,15 @@ int64_t msp_adam_chunks(int64_t n);
 int msp_adam_step(const msp_adam_tensor* table, const int64_t* chunk_start, const float* const* grads, int n,
                   int64_t n_chunks, float* step, int bump, double lr, double beta1, double beta2, double eps,
                   double weight_decay, msp_stream_t stream);
+/* The same launch with the step counts and the hyper-parameters in device memory (additive, ABI 10), for steps
+ * replayed from a captured graph under a learning-rate schedule.  steps: device float [n], one count per tensor;
+ * hyper: device double [5] = lr, beta1, beta2, eps, weight_decay, read by the kernel, so a replay uses what was
+ * last copied there.  For tensor i with a non-NULL gradient every block uses t = steps[i] + 1 (bias corrections in
+ * double on the device) and the element update above; a one-block launch that follows stores steps[i] = t for
+ * exactly those tensors (empty ones included) and leaves the others' counts untouched, as torch.optim.Adam does
+ * for a parameter whose grad is None.  Two launches, nothing read back, no block waits on another. */
+int msp_adam_step_dev(const msp_adam_tensor* table, const int64_t* chunk_start, const float* const* grads, int n,
+                      int64_t n_chunks, float* steps, const double* hyper, msp_stream_t stream);
 
 #ifdef __cplusplus
 }
