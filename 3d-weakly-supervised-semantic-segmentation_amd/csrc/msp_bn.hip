@@ -24,13 +24,8 @@
 namespace msp {
 
 constexpr int kT = 256;
-#ifndef MSP_BN_MAX_PARTS
-#define MSP_BN_MAX_PARTS 1024
-#endif
-constexpr int64_t kMaxParts = MSP_BN_MAX_PARTS;
-#ifndef MSP_BN_UNROLL  // bn_reduce4's rows in flight per thread (experiments: 8)
-#define MSP_BN_UNROLL 4
-#endif
+constexpr int64_t kMaxParts = 1024;  // cap on a reduction's blocks (re-swept in round 6: DESIGN.md §3.11)
+constexpr int kBnUnroll = 4;         // bn_reduce4's rows in flight per thread (8 was neutral: DESIGN.md §3.11)
 
 // Partial-sum blocks: two 4-deep passes of the vector form per block (R = 1024 / C rows per pass, so
 // 8 R rows per block, 16..256), at most kMaxParts.  Sized by C so the small levels (C up to 448, a few
@@ -124,7 +119,7 @@ __global__ __launch_bounds__(kT) void bn_reduce4_kernel(const float* __restrict_
       return e;
     };
     int64_t v = v0 + ro;
-    constexpr int U = MSP_BN_UNROLL;  // rows in flight per thread and tensor
+    constexpr int U = kBnUnroll;  // rows in flight per thread and tensor
     if (MODE == 3) {
       for (; v + (U - 1) * R < v1; v += U * R) {
         float4 e[U];

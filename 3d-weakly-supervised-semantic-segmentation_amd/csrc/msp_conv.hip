@@ -76,97 +76,12 @@ __global__ __launch_bounds__(kThreads) void conv_pairs_kernel(
   }
 }
 
-// Runs of chunks (MSP_PAIRS_RUN): one wave takes `run` consecutive chunks.  The chunks are offset-major, so a run
+// Runs of chunks: one wave takes `run` consecutive chunks.  The chunks are offset-major, so a run
 // stays in one offset except where it crosses into the next; the offset's weight block (c_in / 16 <= KMAX k-steps
 // of NT 16-column groups) is loaded into registers once per run and reloaded only at such a crossing, instead of
 // once per 16 pairs (conv_pairs_kernel reads 2x the bytes of the x rows it multiplies in weights at level 0).
-// The next chunk's pair indices are loaded while the current chunk's x rows are in flight.  Per chunk the
-// arithmetic is conv_pairs_kernel's, in the same order: the outputs are bit-identical.
-template <int NT, int KMAX>
-__global__ __launch_bounds__(kThreads) void conv_pairs_run_kernel(
-    const float* __restrict__ x, int c_in, const float* __restrict__ wt, int K, int c_out,
-    const int32_t* __restrict__ pin, const int32_t* __restrict__ pout, const int64_t* __restrict__ off_start,
-    const int64_t* __restrict__ chunk_start, int64_t n_chunks, int run, float* __restrict__ out) {
-  constexpr int NC = 16 * NT;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t ch0 = ((int64_t)blockIdx.x * kWaves + wave) * run;
-  if (ch0 >= n_chunks) return;
-  const int64_t ch1 = ch0 + run < n_chunks ? ch0 + run : n_chunks;
-  const int c0 = blockIdx.y * NC;
-  const int r = lane & 15, q = lane >> 4;
-  const int kcn = c_in >> 4;
-  // offset walk of the index loads (wave-uniform; empty offsets have equal chunk starts)
-  int oi = find_offset(chunk_start, K, ch0);
-  int64_t oi_first = chunk_start[oi], oi_end = chunk_start[oi + 1], pb = off_start[oi], pe = off_start[oi + 1];
-  auto indices = [&](int64_t ch, int& src, int (&dst)[4], int& o_of) {
-    if (ch >= oi_end) {
-      do {
-        ++oi;
-        oi_end = chunk_start[oi + 1];
-      } while (ch >= oi_end);
-      oi_first = chunk_start[oi];
-      pb = off_start[oi];
-      pe = off_start[oi + 1];
-    }
-    const int64_t p0 = pb + (ch - oi_first) * MSP_CHUNK;
-    src = p0 + r < pe ? pin[p0 + r] : -1;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) dst[j] = p0 + 4 * q + j < pe ? pout[p0 + 4 * q + j] : -1;
-    o_of = oi;
-  };
-  floatx4 b[KMAX][NT];
-  int ow = -1;  // the offset whose weights are in b
-  int src, dst[4], o;
-  indices(ch0, src, dst, o);
-  for (int64_t ch = ch0; ch < ch1; ++ch) {
-    if (o != ow) {
-      ow = o;
-      const float* wb = wt + ((int64_t)o * c_out + c0 + r) * c_in + 4 * q;
-#pragma unroll
-      for (int kc = 0; kc < KMAX; ++kc)
-        if (kc < kcn) {
-#pragma unroll
-          for (int t = 0; t < NT; ++t)
-            b[kc][t] = *reinterpret_cast<const floatx4*>(wb + (int64_t)t * 16 * c_in + kc * 16);
-        }
-    }
-    const float* xs = x + (int64_t)(src < 0 ? 0 : src) * c_in + 4 * q;
-    floatx4 a[KMAX];
-#pragma unroll
-    for (int kc = 0; kc < KMAX; ++kc)
-      if (kc < kcn) {
-        a[kc] = *reinterpret_cast<const floatx4*>(xs + kc * 16);
-        if (src < 0) a[kc] = floatx4{0.f, 0.f, 0.f, 0.f};
-      }
-    int dcur[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) dcur[j] = dst[j];
-    if (ch + 1 < ch1) indices(ch + 1, src, dst, o);
-    floatx4 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kc = 0; kc < KMAX; ++kc)
-      if (kc < kcn) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-#pragma unroll
-          for (int t = 0; t < NT; ++t) acc[t] = mfma4(a[kc][s], b[kc][t][s], acc[t]);
-        }
-      }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (dcur[j] >= 0) {
-        float* d = out + (int64_t)dcur[j] * c_out + c0 + r;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) d[t * 16] = acc[t][j];
-      }
-    }
-  }
-}
-
-// MSP_PAIRS_DEPTH 2: conv_pairs_run_kernel with the next chunk's x rows loaded as well (and the indices two chunks
-// ahead) while the current chunk's MFMAs and stores run.
+// The next chunk's x rows and the pair indices two chunks ahead are loaded while the current chunk's MFMAs and
+// stores run.  Per chunk the arithmetic is conv_pairs_kernel's, in the same order: the outputs are bit-identical.
 template <int NT, int KMAX>
 __global__ __launch_bounds__(kThreads) void conv_pairs_pipe_kernel(
     const float* __restrict__ x, int c_in, const float* __restrict__ wt, int K, int c_out,
@@ -462,12 +377,9 @@ int msp_conv_tile_rows(int64_t n_rows, int c_in, int c_out) {
 
 // Per-wave tiles (x6r) for narrow outputs, and since round 5 for level 0's 32 -> 64 too (two 32-column passes
 // over the gathers, n_y = 2) instead of the shared tiles (x6d: mfma_busy 0.15 there, 0.83 ms per call): 49.73-49.81
-// vs 50.07-50.11 ms/step (profiles/r05/ab_r05am_x6r_wide.log).  MSP_X6R_WIDE 0: the round-4 choice.
-#ifndef MSP_X6R_WIDE
-#define MSP_X6R_WIDE 1
-#endif
+// vs 50.07-50.11 ms/step (profiles/r05/ab_r05am_x6r_wide.log).
 static bool use_x6r(int64_t n_rows, int c_in, int c_out) {
-  return (c_out <= 32 && c_in <= 64) || (MSP_X6R_WIDE && c_out == 64 && c_in <= 32 && n_rows >= 100000);
+  return (c_out <= 32 && c_in <= 64) || (c_out == 64 && c_in <= 32 && n_rows >= 100000);
 }
 
 int msp_conv_tile_form(int64_t n_rows, int c_in, int c_out, int tile_rows) {
@@ -524,20 +436,12 @@ int msp_conv_tile_bn(const float* x, int c_in, const float* wt, int K, int flip,
   return rc ? rc : check_launch("msp_conv_tile");
 }
 
-// Runs of chunks with the weights in registers where c_in <= 64; MSP_PAIRS_RUN 0: one chunk per wave, weights
-// re-read per chunk (the round-4 form).  Level 0 of the headline batch (64 -> 32, 1.30 M pairs): 148.8 us in the
-// one-chunk form, 137.6 with runs (MSP_PAIRS_DEPTH 1: indices one chunk ahead), 123.5 with the x rows one chunk
-// ahead as well (MSP_PAIRS_DEPTH 2); 4096 waves instead of 8192: 133.1 (profiles/r05/kb_pairs_r05b.log).  Without
-// any prefetch the runs were slower than the one-chunk form (163 vs 150 us).
-#ifndef MSP_PAIRS_RUN
-#define MSP_PAIRS_RUN 1
-#endif
-#ifndef MSP_PAIRS_WAVES
-#define MSP_PAIRS_WAVES 8192
-#endif
-#ifndef MSP_PAIRS_DEPTH
-#define MSP_PAIRS_DEPTH 2
-#endif
+// Runs of chunks with the weights in registers where c_in <= 64 (the round-4 form: one chunk per wave, weights
+// re-read per chunk).  Level 0 of the headline batch (64 -> 32, 1.30 M pairs): 148.8 us in the one-chunk form, 137.6
+// with runs and the indices one chunk ahead, 123.5 with the x rows one chunk ahead as well (the form kept); 4096
+// waves instead of 8192: 133.1 (profiles/r05/kb_pairs_r05b.log).  Without any prefetch the runs were slower than
+// the one-chunk form (163 vs 150 us).
+constexpr int64_t kPairsWaves = 8192;  // waves the runs are sized for
 
 int msp_conv_pairs(const float* x, int c_in, const float* wt, int K, int c_out, const int32_t* pair_in,
                    const int32_t* pair_out, const int64_t* off_start, const int64_t* chunk_start,
@@ -547,23 +451,19 @@ int msp_conv_pairs(const float* x, int c_in, const float* wt, int K, int c_out, 
   if (n_chunks == 0) return MSP_OK;
   hipStream_t s = as_stream(stream);
   const int kcn = c_in / 16, n16 = c_out / 16;
-  if (MSP_PAIRS_RUN && kcn <= 4) {
+  if (kcn <= 4) {
     // weights in registers (c_in <= 64); wider inputs keep the one-chunk form, which measured faster there (the
     // weight registers cost occupancy and narrower column groups re-read x: profiles/r05/kb_pairs_r05*.log)
     const int NT = pick_tile(n16), ny = n16 / NT;
-    // about MSP_PAIRS_WAVES waves over the grid: runs long enough to amortise the weights, enough waves to fill
+    // about kPairsWaves waves over the grid: runs long enough to amortise the weights, enough waves to fill
     // the chip
-    int64_t run = n_chunks * ny / MSP_PAIRS_WAVES;
+    int64_t run = n_chunks * ny / kPairsWaves;
     run = run < 1 ? 1 : run > 16 ? 16 : run;
     const int64_t waves = ceil_div(n_chunks, run);
     dim3 grid((unsigned)ceil_div(waves, kWaves), (unsigned)ny);
-#define LAUNCH_RUN(N)                                                                                          \
-  if (MSP_PAIRS_DEPTH == 2)                                                                                    \
-    conv_pairs_pipe_kernel<N, 4><<<grid, kThreads, 0, s>>>(x, c_in, wt, K, c_out, pair_in, pair_out, off_start, \
-                                                           chunk_start, n_chunks, (int)run, out);              \
-  else                                                                                                         \
-    conv_pairs_run_kernel<N, 4><<<grid, kThreads, 0, s>>>(x, c_in, wt, K, c_out, pair_in, pair_out, off_start,  \
-                                                          chunk_start, n_chunks, (int)run, out)
+#define LAUNCH_RUN(N)                                                                                        \
+  conv_pairs_pipe_kernel<N, 4><<<grid, kThreads, 0, s>>>(x, c_in, wt, K, c_out, pair_in, pair_out, off_start, \
+                                                         chunk_start, n_chunks, (int)run, out)
     switch (NT) {
       case 1: LAUNCH_RUN(1); break;
       case 2: LAUNCH_RUN(2); break;

@@ -34,8 +34,6 @@
 #include "msp_x6.h"
 #include "msp_bn_epi.h"
 
-#include <cstdlib>
-
 namespace msp {
 
 // wt [K][c_out][c_in] fp32 -> the per-step LDS images of conv_x6d_kernel:
@@ -62,16 +60,16 @@ __global__ __launch_bounds__(256) void split_weights_kernel(const float* __restr
 //   weights(s+1+D) load | rows + gathers(s+D) | sources(s+2D)
 // so every load has D steps to land.  Step descriptors come from a packed
 // per-offset table in LDS (one read per step, for step s + 2D).
-// ABL (timing experiments only, wrong results): bit 1 no barrier, 2 no
-// gathers, 4 no LDS accumulation, 8 no weight staging, 16 no split, 32 no MFMA.
+// KS = 32-deep k-slices, D = 2 and TR = 128-row tiles: see plan_x6 below.
 // NB = weight slice buffers: 2 (one barrier per step) or 1 (a second barrier
 // before the slice is overwritten; 12 KiB less LDS -> 3 blocks per CU).
-template <int NT, int KS, int D, int TR, int ABL = 0, int NB = 2>
+template <int NT, int NB>
 __global__ __launch_bounds__(kThreads) void conv_x6d_kernel(
     const float* __restrict__ x, int c_in, const u32x4* __restrict__ wimg, int K, int flip, int c_out,
     const int64_t* __restrict__ tile_start, const uint8_t* __restrict__ chunk_off,
     const int32_t* __restrict__ chunk_src, const uint16_t* __restrict__ chunk_row, int64_t n_rows, int n_y,
     int n_split, float* __restrict__ out) {
+  constexpr int KS = 32, D = 2, TR = 128;
   static_assert(D >= 2, "the weight slot of step s+1 must differ from step s's");
   constexpr int NC = 16 * NT;
   constexpr int K8 = KS / 8;
@@ -212,13 +210,8 @@ __global__ __launch_bounds__(kThreads) void conv_x6d_kernel(
       for (int kk = 0; kk < NKK; ++kk) {
         const int k = min(sd.ks * KS + kk * 32 + 8 * q, c_in - 8);
         const floatx4* pv = reinterpret_cast<const floatx4*>(xb + (ro + 4u * (uint32_t)k));
-        if (ABL & 2) {
-          v.a[j][kk][0] = floatx4{(float)sv.v[j], (float)k, 1.f, 2.f};
-          v.a[j][kk][1] = floatx4{(float)k, (float)sv.v[j], 3.f, 4.f};
-        } else {
-          v.a[j][kk][0] = pv[0];
-          v.a[j][kk][1] = pv[1];
-        }
+        v.a[j][kk][0] = pv[0];
+        v.a[j][kk][1] = pv[1];
       }
     }
   };
@@ -237,16 +230,7 @@ __global__ __launch_bounds__(kThreads) void conv_x6d_kernel(
         u32x4 xp[MJ][3];
 #pragma unroll
         for (int j = 0; j < MJ; ++j)
-          if (j < sd.gn) {
-            if (ABL & 16) {
-#pragma unroll
-              for (int pp = 0; pp < 3; ++pp)
-                xp[j][pp] = u32x4{__float_as_uint(v.a[j][kk][0][pp]), __float_as_uint(v.a[j][kk][0][pp + 1]),
-                                  __float_as_uint(v.a[j][kk][1][pp]), __float_as_uint(v.a[j][kk][1][pp + 1])};
-            } else {
-              split8(v.a[j][kk][0], v.a[j][kk][1], xp[j]);
-            }
-          }
+          if (j < sd.gn) split8(v.a[j][kk][0], v.a[j][kk][1], xp[j]);
         const int k8 = kk * 4 + q;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
@@ -256,9 +240,7 @@ __global__ __launch_bounds__(kThreads) void conv_x6d_kernel(
           const u32x4 w2 = wb[(2 * K8 + k8) * NC + un];
 #pragma unroll
           for (int j = 0; j < MJ; ++j) {
-            if (j < sd.gn && (ABL & 32)) {
-              acc[j][t] += __builtin_bit_cast(floatx4, w0 ^ w1 ^ w2 ^ xp[j][0] ^ xp[j][1] ^ xp[j][2]);
-            } else if (j < sd.gn) {
+            if (j < sd.gn) {
               floatx4 a = acc[j][t];
               a = mfma_bf16(w2, xp[j][0], a);
               a = mfma_bf16(w1, xp[j][1], a);
@@ -322,25 +304,14 @@ __global__ __launch_bounds__(kThreads) void conv_x6d_kernel(
     for (int k = 0; k < D; ++k) {
       const int s = base + k;
       const int k1 = (k + 1) % D;
-      if (!(ABL & 1)) __syncthreads();  // wbuf[s & 1] holds step s's slice; step s-1's LDS updates are done
+      __syncthreads();  // wbuf[s & 1] holds step s's slice; step s-1's LDS updates are done
       mma(Vd[k], (s & 1) % NB, V[k]);
       consume_val(V[k]);
-      if (!(ABL & 4)) {
-        rmw(Vd[k], R[k]);
-      } else if (Vd[k].gn > 0) {
-        floatx4 z = acc[0][0];
-#pragma unroll
-        for (int j = 0; j < MJ; ++j)
-#pragma unroll
-          for (int t = 0; t < NT; ++t) z += acc[j][t];
-        acc4[lane] += z;
-      }
+      rmw(Vd[k], R[k]);
       consume_row(R[k]);
-      if (!(ABL & 8)) {
-        if (NB == 1) __syncthreads();  // every wave is done with step s's slice
-        st_w(Wr[k1], ((s + 1) & 1) % NB);  // step s+1's slice (loaded D steps ago)
-        ld_w(Sd[k1], Wr[k1]);       // step s+1+D
-      }
+      if (NB == 1) __syncthreads();  // every wave is done with step s's slice
+      st_w(Wr[k1], ((s + 1) & 1) % NB);  // step s+1's slice (loaded D steps ago)
+      ld_w(Sd[k1], Wr[k1]);              // step s+1+D
       Vd[k] = Sd[k];
       ld_row(Vd[k], R[k]);  // step s+D
       gather(Vd[k], S[k], V[k]);
@@ -378,37 +349,18 @@ __global__ __launch_bounds__(kThreads) void conv_x6d_kernel(
 // weight sets in registers: the current run's and the next run's, loaded at
 // the current run's first chunk (uniform branches; the chunk values keep
 // their D-deep pipeline across runs).
-// TR: output rows per wave tile (128, or 64: half the LDS accumulator tile per wave, so twice the blocks per CU).
-#ifdef MSP_EXPERIMENTS
-// x [n][c] fp32 (c % 32 == 0) -> its exact split image: row i, 32-channel slice kk, piece p, k-octet q at 16-byte
-// unit (i * c / 32 + kk) * 12 + p * 4 + q.  One thread per (row, k-octet).
-__global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict__ x, int64_t n, int c,
-                                                         u32x4* __restrict__ img) {
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int oc = c / 8;
-  if (g >= n * oc) return;
-  const int64_t row = g / oc;
-  const int o = (int)(g - row * oc), kk = o >> 2, q = o & 3;
-  const floatx4* src = reinterpret_cast<const floatx4*>(x + row * c + 8 * o);
-  u32x4 pc[3];
-  split8(src[0], src[1], pc);
-  u32x4* dst = img + (row * (c / 32) + kk) * 12 + q;
-#pragma unroll
-  for (int p = 0; p < 3; ++p) dst[p * 4] = pc[p];
-}
-#endif
-
-// PS 1 (experiments build only; measured slower): x is the exact split image of the input rows (split_rows_kernel: per row and 32-channel slice, 3 pieces x 4
-// k-octets of 16 bytes, row stride 6 c_in bytes), so the chunk loop loads the pieces instead of splitting every
-// gathered row per rule.
+// Chunk values D = 3 deep and 128-row tiles (64-row tiles and D = 2 were slower: profiles/r03/kbexp_r03x6r.log,
+// profiles/r06/kbexp_r06ad_x6r_depth.log); loading pre-split rows instead of splitting every gathered row per rule
+// measured slower.
 // EPI (msp_bn_epilogue, round 6): the BatchNorm sums of the rows written; its own instantiation, so the plain form
 // compiles exactly as before.
-template <int NT, int NKK, int D, int NW, int TR = 128, int PS = 0, bool EPI = false>
+template <int NT, int NKK, bool EPI = false>
 __global__ __launch_bounds__(kThreads) void conv_x6r_kernel(
     const float* __restrict__ x, int c_in, const u32x4* __restrict__ wimg, int K, int flip, int c_out,
     const int64_t* __restrict__ tile_start, const uint8_t* __restrict__ chunk_off,
     const int32_t* __restrict__ chunk_src, const uint16_t* __restrict__ chunk_row, int64_t n_rows,
     int64_t n_tiles, int n_y, float* __restrict__ out, BnEpi epi) {
+  constexpr int D = 3, TR = 128;
   constexpr int NC = 16 * NT;
   constexpr int WU = 3 * 4 * NC;  // 16-byte units of one (offset, k-slice) image
   __shared__ floatx4 lds4[kWaves][TR * NC / 4];
@@ -470,7 +422,7 @@ __global__ __launch_bounds__(kThreads) void conv_x6r_kernel(
     int src, row;
   };
   struct Val {
-    floatx4 a[NKK][PS ? 3 : 2];
+    floatx4 a[NKK][2];
   };
   auto ld_idx = [&](int64_t c, St& d) {
     const int64_t cc = c < clast ? c : clast;
@@ -478,14 +430,6 @@ __global__ __launch_bounds__(kThreads) void conv_x6r_kernel(
     d.row = chunk_row[cc * MSP_CHUNK + r];
   };
   auto ld_val = [&](const St& d, Val& v) {
-    if constexpr (PS) {  // the row's units (kk, p, q): 16 bytes each, 12 per 32-channel slice
-      const floatx4* xs = reinterpret_cast<const floatx4*>(x) + (uint32_t)d.src * (uint32_t)(NKK * 12) + q;
-#pragma unroll
-      for (int kk = 0; kk < NKK; ++kk)
-#pragma unroll
-        for (int p = 0; p < 3; ++p) v.a[kk][p] = xs[kk * 12 + p * 4];
-      return;
-    }
     const char* xs = reinterpret_cast<const char*>(x) + (uint32_t)d.src * (uint32_t)c_in * 4u;
 #pragma unroll
     for (int kk = 0; kk < NKK; ++kk) {
@@ -502,12 +446,7 @@ __global__ __launch_bounds__(kThreads) void conv_x6r_kernel(
 #pragma unroll
     for (int kk = 0; kk < NKK; ++kk) {
       u32x4 xp[3];
-      if constexpr (PS) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p) xp[p] = __builtin_bit_cast(u32x4, v.a[kk][p]);
-      } else {
-        split8(v.a[kk][0], v.a[kk][1], xp);
-      }
+      split8(v.a[kk][0], v.a[kk][1], xp);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         floatx4 c = acc[t];
@@ -554,10 +493,7 @@ __global__ __launch_bounds__(kThreads) void conv_x6r_kernel(
       }
       if (i < n) run(S[k], Wc, rowR[k]);
 #pragma unroll
-      for (int kk = 0; kk < NKK; ++kk) {
-        asm volatile("" ::"v"(S[k].a[kk][0]), "v"(S[k].a[kk][1]));
-        if constexpr (PS) asm volatile("" ::"v"(S[k].a[kk][PS ? 2 : 0]));
-      }
+      for (int kk = 0; kk < NKK; ++kk) asm volatile("" ::"v"(S[k].a[kk][0]), "v"(S[k].a[kk][1]));
       ld_val(J[k], S[k]);  // chunk c+k+D
       rowR[k] = J[k].row;
       ld_idx(c + k + 2 * D, J[k]);
@@ -632,11 +568,11 @@ int launch_x6r(const float* x, int c_in, const float* wt, int K, int flip, int c
 #define LR(N, C)                                                                                               \
   if (NT == N && NKK == C) {                                                                                   \
     if (epi)                                                                                                   \
-      conv_x6r_kernel<N, C, 3, 2, 128, 0, true><<<grid, kThreads, 0, s>>>(                                     \
-          x, c_in, wimg, K, flip, c_out, tile_start, chunk_off, chunk_src, chunk_row, n_rows, n_tiles, n_y, out, be); \
-    else                                                                                                       \
-      conv_x6r_kernel<N, C, 3, 2><<<grid, kThreads, 0, s>>>(x, c_in, wimg, K, flip, c_out, tile_start, chunk_off, \
+      conv_x6r_kernel<N, C, true><<<grid, kThreads, 0, s>>>(x, c_in, wimg, K, flip, c_out, tile_start, chunk_off, \
                                                             chunk_src, chunk_row, n_rows, n_tiles, n_y, out, be); \
+    else                                                                                                       \
+      conv_x6r_kernel<N, C><<<grid, kThreads, 0, s>>>(x, c_in, wimg, K, flip, c_out, tile_start, chunk_off,    \
+                                                      chunk_src, chunk_row, n_rows, n_tiles, n_y, out, be);    \
     return MSP_OK;                                                                                             \
   }
   LR(2, 1) LR(2, 2) LR(1, 1) LR(1, 2)
@@ -647,57 +583,6 @@ int launch_x6r(const float* x, int c_in, const float* wt, int K, int flip, int c
 
 
 size_t x6p_ws_bytes(int K, int c_in, int c_out) { return (size_t)K * c_out * ((c_in + 31) / 32) * 32 * 6; }
-
-#ifdef MSP_EXPERIMENTS
-// Per-wave form with the tile height and pipeline depth as parameters (scripts/kbench.py, experiments build):
-// variant = 10 * D + (tile_rows == 64); the rulebook must have tile_rows-row tiles.
-int launch_x6r_exp(int variant, const float* x, int c_in, const float* wt, int K, int flip, int c_out,
-                   int tile_rows, const int64_t* tile_start, const uint8_t* chunk_off, const int32_t* chunk_src,
-                   const uint16_t* chunk_row, int64_t n_rows, float* out, void* ws, hipStream_t s) {
-  const int NT = c_out / 16 >= 2 && (c_out / 16) % 2 == 0 ? 2 : 1;
-  const int NKK = (c_in + 31) / 32;
-  const int n_y = c_out / (16 * NT);
-  const int64_t n_tiles = ceil_div(n_rows, tile_rows);
-  u32x4* wimg = static_cast<u32x4*>(ws);
-  const int64_t units = (int64_t)K * c_out * NKK * 32 * 6 / 16;
-  split_weights_kernel<<<(unsigned)ceil_div(units, 256), 256, 0, s>>>(wt, K, c_out, c_in, 16 * NT, 32, wimg,
-                                                                       (flip >> 1) & 1);
-  flip &= 1;
-  const unsigned grid = (unsigned)(ceil_div(n_tiles, kWaves) * n_y);
-  // variant 100 + v: pre-split rows (the split pass into the workspace past the weight image, then the PS kernel);
-  // 200 + v: the PS kernel alone on whatever the workspace holds (timing only)
-  const int ps = variant / 100;
-  variant %= 100;
-  const int D = variant / 10, T = variant % 10 == 1 ? 64 : 128;
-  if (T != tile_rows) return MSP_EINVAL;
-  const float* xin = x;
-  if (ps) {
-    if (c_in % 32) return MSP_EINVAL;
-    u32x4* img = wimg + (units + 63) / 64 * 64;
-    if (ps == 1)
-      split_rows_kernel<<<(unsigned)ceil_div(n_rows * (c_in / 8), 256), 256, 0, s>>>(x, n_rows, c_in, img);
-    xin = reinterpret_cast<const float*>(img);
-  }
-#define LE(N, C, DD, TT)                                                                                        \
-  if (NT == N && NKK == C && D == DD && T == TT) {                                                             \
-    if (ps)                                                                                                    \
-      conv_x6r_kernel<N, C, DD, 2, TT, 1><<<grid, kThreads, 0, s>>>(xin, c_in, wimg, K, flip, c_out,           \
-                                                                    tile_start, chunk_off, chunk_src,          \
-                                                                    chunk_row, n_rows, n_tiles, n_y, out,      \
-                                                                    BnEpi{});                                  \
-    else                                                                                                       \
-      conv_x6r_kernel<N, C, DD, 2, TT><<<grid, kThreads, 0, s>>>(x, c_in, wimg, K, flip, c_out, tile_start,    \
-                                                                 chunk_off, chunk_src, chunk_row, n_rows,      \
-                                                                 n_tiles, n_y, out, BnEpi{});                  \
-    return MSP_OK;                                                                                             \
-  }
-  LE(2, 1, 3, 128) LE(2, 1, 3, 64) LE(2, 1, 2, 128) LE(2, 1, 2, 64)
-  LE(2, 2, 3, 128) LE(2, 2, 3, 64) LE(2, 2, 2, 64) LE(2, 2, 2, 128)
-#undef LE
-  set_error("launch_x6r_exp: no variant %d for c_in=%d c_out=%d", variant, c_in, c_out);
-  return MSP_EINVAL;
-}
-#endif
 
 // ---------------------------------------------------------------- one contribution per output row, split-bf16
 // msp_conv_pairs_x6 (round 6): the deconvolution forward and the strided convolution's backward-data -- every
@@ -760,9 +645,10 @@ __global__ __launch_bounds__(kThreads) void conv_pairs_x6_kernel(
 
 // The same over a run of consecutive chunks per wave (c_in <= 32 KK): the next chunk's x rows are loaded and the
 // indices two chunks ahead read while the current chunk's MFMAs and stores run (the latency chain index -> row
-// gather -> MFMA -> scattered store is what bounds the one-chunk form: 2.5 TB/s and 43 TF/s at level 0).  WREG
-// keeps the offset's weight fragments in registers across the run (reloaded when the run crosses an offset).
-template <int NT, int KK, bool WREG>
+// gather -> MFMA -> scattered store is what bounds the one-chunk form: 2.5 TB/s and 43 TF/s at level 0).  The
+// offset's weight fragments stay in registers across the run (reloaded when the run crosses an offset; reading them
+// per chunk was slower: profiles/r06/pairs_bench_r06pb.log).
+template <int NT, int KK>
 __global__ __launch_bounds__(kThreads) void conv_pairs_x6_pipe_kernel(
     const float* __restrict__ x, int c_in, const u32x4* __restrict__ wimg, int K, int c_out,
     const int32_t* __restrict__ pin, const int32_t* __restrict__ pout, const int64_t* __restrict__ off_start,
@@ -806,7 +692,7 @@ __global__ __launch_bounds__(kThreads) void conv_pairs_x6_pipe_kernel(
         a[kk][1] = *reinterpret_cast<const floatx4*>(xs + k + 4);
       }
   };
-  u32x4 w[WREG ? KK : 1][NT][3];
+  u32x4 w[KK][NT][3];
   int ow = -1;
   int s_c, d_c, o_c, s_n = -1, d_n = -1, o_n = 0;
   floatx4 a[KK][2];
@@ -815,7 +701,7 @@ __global__ __launch_bounds__(kThreads) void conv_pairs_x6_pipe_kernel(
   if (ch0 + 1 < ch1) indices(ch0 + 1, s_n, d_n, o_n);
   for (int64_t ch = ch0; ch < ch1; ++ch) {
     const u32x4* wo = wimg + ((int64_t)o_c * n_y + cy) * nkk * WU + q * NC + r;
-    if (WREG && o_c != ow) {
+    if (o_c != ow) {
       ow = o_c;
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk)
@@ -823,7 +709,7 @@ __global__ __launch_bounds__(kThreads) void conv_pairs_x6_pipe_kernel(
 #pragma unroll
           for (int t = 0; t < NT; ++t)
 #pragma unroll
-            for (int j = 0; j < 3; ++j) w[WREG ? kk : 0][t][j] = wo[kk * WU + j * 4 * NC + 16 * t];
+            for (int j = 0; j < 3; ++j) w[kk][t][j] = wo[kk * WU + j * 4 * NC + 16 * t];
         }
     }
     const bool more = ch + 1 < ch1;
@@ -843,16 +729,7 @@ __global__ __launch_bounds__(kThreads) void conv_pairs_x6_pipe_kernel(
         split8(lo, hi4, xp);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-          u32x4 w0, w1, w2;
-          if (WREG) {
-            w0 = w[WREG ? kk : 0][t][0];
-            w1 = w[WREG ? kk : 0][t][1];
-            w2 = w[WREG ? kk : 0][t][2];
-          } else {
-            w0 = wo[kk * WU + 0 * 4 * NC + 16 * t];
-            w1 = wo[kk * WU + 1 * 4 * NC + 16 * t];
-            w2 = wo[kk * WU + 2 * 4 * NC + 16 * t];
-          }
+          const u32x4 w0 = w[kk][t][0], w1 = w[kk][t][1], w2 = w[kk][t][2];
           floatx4 c = mfma_bf16(w2, xp[0], floatx4{0.f, 0.f, 0.f, 0.f});
           c = mfma_bf16(w1, xp[1], c);
           c = mfma_bf16(w0, xp[2], c);
@@ -894,14 +771,15 @@ __global__ __launch_bounds__(kThreads) void conv_pairs_x6_pipe_kernel(
 // 30-55 % of a group's (offset, row) slots at levels 0-2, but every wave of a
 // block does the same steps, so the block shares each step's split weight
 // slice through LDS (double buffered, one barrier per step, staged from
-// registers loaded two steps ahead) instead of reloading it per wave.
+// registers loaded one step ahead) instead of reloading it per wave.
 // Gathered values run two steps ahead, neighbour indices four; each step's six
 // piece products are summed in a zeroed accumulator and added once.
-template <int NT, int G, int OCC = 1, int LR = 0, int NW = kWaves>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(OCC))) void conv_x6g_kernel(
+template <int NT>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void conv_x6g_kernel(
     const float* __restrict__ x, int c_in, const u32x4* __restrict__ wimg, int K, int flip, int c_out,
     const int32_t* __restrict__ nbr, const int32_t* __restrict__ perm, int64_t n_rows, int n_y,
     float* __restrict__ out) {
+  constexpr int G = 1, NW = kWaves;  // ONE 16-row group per wave at 4 waves per SIMD (launch_x6g)
   constexpr int NC = 16 * NT;
   constexpr int WU = 3 * 4 * NC;  // 16-byte units of one step's split weight slice
   constexpr int TRW = 16 * G;     // rows per wave
@@ -986,84 +864,53 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(OCC))) 
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[g][t] = floatx4{0.f, 0.f, 0.f, 0.f};
   auto run = [&](int buf, const Xv& v, uint32_t am) {
-    if constexpr (LR) {
-      // column group outer: three weight fragments live at a time
-      u32x4 xp[G][3];
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const bool lo = (v.ok >> g) & 1;
-        const floatx4 z = {0.f, 0.f, 0.f, 0.f};
-        if ((am >> g) & 1) split8(lo ? v.a[g][0] : z, lo ? v.a[g][1] : z, xp[g]);
-      }
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const u32x4 w0 = wl[buf][(0 * 4 + q) * NC + 16 * t + r];
-        const u32x4 w1 = wl[buf][(1 * 4 + q) * NC + 16 * t + r];
-        const u32x4 w2 = wl[buf][(2 * 4 + q) * NC + 16 * t + r];
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          if ((am >> g) & 1) {  // wave-uniform
-            floatx4 c = {0.f, 0.f, 0.f, 0.f};
-            c = mfma_bf16(w2, xp[g][0], c);
-            c = mfma_bf16(w1, xp[g][1], c);
-            c = mfma_bf16(w0, xp[g][2], c);
-            c = mfma_bf16(w1, xp[g][0], c);
-            c = mfma_bf16(w0, xp[g][1], c);
-            acc[g][t] += mfma_bf16(w0, xp[g][0], c);
-          }
-        }
-      }
-      return;
-    }
-    u32x4 w[NT][3];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int p = 0; p < 3; ++p) w[t][p] = wl[buf][(p * 4 + q) * NC + 16 * t + r];
+    // column group outer: three weight fragments live at a time
+    u32x4 xp[G][3];
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-      if ((am >> g) & 1) {  // wave-uniform
-        const bool lo = (v.ok >> g) & 1;
-        const floatx4 z = {0.f, 0.f, 0.f, 0.f};
-        u32x4 xp[3];
-        split8(lo ? v.a[g][0] : z, lo ? v.a[g][1] : z, xp);
+      const bool lo = (v.ok >> g) & 1;
+      const floatx4 z = {0.f, 0.f, 0.f, 0.f};
+      if ((am >> g) & 1) split8(lo ? v.a[g][0] : z, lo ? v.a[g][1] : z, xp[g]);
+    }
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {  // the step's six products summed apart, then added once
+    for (int t = 0; t < NT; ++t) {
+      const u32x4 w0 = wl[buf][(0 * 4 + q) * NC + 16 * t + r];
+      const u32x4 w1 = wl[buf][(1 * 4 + q) * NC + 16 * t + r];
+      const u32x4 w2 = wl[buf][(2 * 4 + q) * NC + 16 * t + r];
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        if ((am >> g) & 1) {  // wave-uniform
           floatx4 c = {0.f, 0.f, 0.f, 0.f};
-          c = mfma_bf16(w[t][2], xp[0], c);
-          c = mfma_bf16(w[t][1], xp[1], c);
-          c = mfma_bf16(w[t][0], xp[2], c);
-          c = mfma_bf16(w[t][1], xp[0], c);
-          c = mfma_bf16(w[t][0], xp[1], c);
-          acc[g][t] += mfma_bf16(w[t][0], xp[0], c);
+          c = mfma_bf16(w2, xp[g][0], c);
+          c = mfma_bf16(w1, xp[g][1], c);
+          c = mfma_bf16(w0, xp[g][2], c);
+          c = mfma_bf16(w1, xp[g][0], c);
+          c = mfma_bf16(w0, xp[g][1], c);
+          acc[g][t] += mfma_bf16(w0, xp[g][0], c);
         }
       }
     }
   };
-  constexpr int NS = LR ? 1 : 2;  // weight staging slots (slices loaded NS steps ahead)
-  Wst S[2];
+  Wst S;  // one weight staging slot (slices loaded one step ahead)
   Ix I[2];
   Xv X[2];
   uint32_t am[2];
-  ld_wst(0, S[0]);
-  if (NS == 2) ld_wst(1, S[1]);
+  ld_wst(0, S);
   ld_ix(0, I[0]);
   ld_ix(1, I[1]);
-  st_wst(S[0], 0);
-  ld_wst(NS == 2 ? 2 : 1, S[0]);
+  st_wst(S, 0);
+  ld_wst(1, S);
   am[0] = ld_x(0, I[0], X[0]);
   am[1] = ld_x(1, I[1], X[1]);
   ld_ix(2, I[0]);
   ld_ix(3, I[1]);
   // step s (slot k = s & 1): wl[k] holds its weight slice, X[k] its values,
-  // S[k ^ 1] (S[0] with one slot) the slice of s + 1, I[k] the indices of
-  // s + 2, I[k ^ 1] of s + 3
+  // S the slice of s + 1, I[k] the indices of s + 2, I[k ^ 1] of s + 3
   auto step = [&](int s, auto kc) {
     constexpr int k = decltype(kc)::value;
-    constexpr int sk = NS == 2 ? (k ^ 1) : 0;
     __syncthreads();
-    st_wst(S[sk], k ^ 1);
-    ld_wst(s + 1 + NS, S[sk]);
+    st_wst(S, k ^ 1);
+    ld_wst(s + 2, S);
     run(k, X[k], s < n_steps ? am[k] : 0u);
     am[k] = ld_x(s + 2, I[k], X[k]);
     ld_ix(s + 4, I[k]);
@@ -1105,8 +952,7 @@ int launch_x6g(const float* x, int c_in, const float* wt, int K, int flip, int c
   const unsigned grid = (unsigned)(ceil_div(n_rows, (int64_t)kWaves * 16) * n_y);
 #define LL(N)                                                                                                 \
   if (nt == N) {                                                                                              \
-    conv_x6g_kernel<N, 1, 4, 1><<<grid, kThreads, 0, s>>>(x, c_in, wimg, K, flip, c_out, nbr, perm, n_rows,    \
-                                                          n_y, out);                                          \
+    conv_x6g_kernel<N><<<grid, kThreads, 0, s>>>(x, c_in, wimg, K, flip, c_out, nbr, perm, n_rows, n_y, out);   \
     return MSP_OK;                                                                                            \
   }
   LL(4) LL(3) LL(2) LL(1)
@@ -1133,8 +979,6 @@ size_t x6g_ws_bytes(int K, int c_in, int c_out) { return (size_t)K * c_out * ((c
 // super-steps round-robin, two register sets deep; positions past the piece
 // are clamped to its last pair and their x values zeroed (uniform branch:
 // only the last super-step of a wave in a piece can be partial).
-// ABL (timing only, bits): 1 = no splits (raw bits as the pieces), 2 = no MFMAs, 4 = no row loads,
-// 8 = no pair-list loads.
 // d[j] = v of lane B + j of this lane's row of 16 (DPP row_newbcast), j = 0 .. 7
 template <int B, int... J>
 __device__ __forceinline__ void row_bcast8_(int32_t v, int32_t (&d)[8], std::integer_sequence<int, J...>) {
@@ -1145,8 +989,8 @@ __device__ __forceinline__ void row_bcast8(int32_t v, int32_t (&d)[8]) {
   row_bcast8_<B>(v, d, std::make_integer_sequence<int, 8>{});
 }
 
-template <int WA, int WB, int ABL = 0, int D = 2>
-__global__ __launch_bounds__(kThreads, D == 1 ? 4 : 1) void wgrad_x6_kernel(
+template <int WA, int WB>
+__global__ __launch_bounds__(kThreads, 1) void wgrad_x6_kernel(
     const float* __restrict__ x, int c_in, const float* __restrict__ dy, int c_out,
     const int32_t* __restrict__ pin, const int32_t* __restrict__ pout, const int64_t* __restrict__ off_start,
     int K, int64_t n_pieces, int n_ty, float* __restrict__ slab) {
@@ -1183,7 +1027,7 @@ __global__ __launch_bounds__(kThreads, D == 1 ? 4 : 1) void wgrad_x6_kernel(
   const int32_t* pix = r < 8 ? pin : pout;
   auto ld_idx = [&](int64_t g, Ix& d) {
     const int64_t pc = min(g + 8 * q + (r & 7), p1 - 1);
-    d.w = (ABL & 8) ? (int32_t)(pc >> 4) : pix[pc];  // ABL 8 (timing only): synthetic rows, pc / 16 < n_rows
+    d.w = pix[pc];
   };
   const float* xm = x + m0 + WA * r;
   const float* dyn = dy + n0 + WB * r;
@@ -1193,15 +1037,8 @@ __global__ __launch_bounds__(kThreads, D == 1 ? 4 : 1) void wgrad_x6_kernel(
     row_bcast8<8>(d.w, oo);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      if (ABL & 4) {  // timing only: values from the indices instead of the row loads
-#pragma unroll
-        for (int i = 0; i < WA; ++i) v.a[k][i] = (float)(ii[k] + i) * 1e-6f;
-#pragma unroll
-        for (int t = 0; t < WB; ++t) v.b[k][t] = (float)(oo[k] + t) * 1e-6f;
-      } else {
-        load_vec<WA>(xm + (int64_t)ii[k] * c_in, v.a[k]);
-        load_vec<WB>(dyn + (int64_t)oo[k] * c_out, v.b[k]);
-      }
+      load_vec<WA>(xm + (int64_t)ii[k] * c_in, v.a[k]);
+      load_vec<WB>(dyn + (int64_t)oo[k] * c_out, v.b[k]);
     }
   };
   auto compute = [&](int64_t g, Vals& v) {
@@ -1213,31 +1050,17 @@ __global__ __launch_bounds__(kThreads, D == 1 ? 4 : 1) void wgrad_x6_kernel(
 #pragma unroll
         for (int i = 0; i < WA; ++i) a[k][i] = pp + k < p1 ? a[k][i] : 0.f;
     }
-    auto split = [&](const floatx4& lo, const floatx4& hi, u32x4 (&pc)[3]) {
-      if (ABL & 1) {
-#pragma unroll
-        for (int pp = 0; pp < 3; ++pp)
-          pc[pp] = u32x4{__float_as_uint(lo[pp]), __float_as_uint(lo[pp + 1]), __float_as_uint(hi[pp]),
-                         __float_as_uint(hi[pp + 1])};
-      } else {
-        split8(lo, hi, pc);
-      }
-    };
     u32x4 bp[WB][3];
 #pragma unroll
     for (int t = 0; t < WB; ++t)
-      split(floatx4{v.b[0][t], v.b[1][t], v.b[2][t], v.b[3][t]}, floatx4{v.b[4][t], v.b[5][t], v.b[6][t], v.b[7][t]},
-            bp[t]);
+      split8(floatx4{v.b[0][t], v.b[1][t], v.b[2][t], v.b[3][t]}, floatx4{v.b[4][t], v.b[5][t], v.b[6][t], v.b[7][t]},
+             bp[t]);
 #pragma unroll
     for (int i = 0; i < WA; ++i) {
       u32x4 ap[3];
-      split(floatx4{a[0][i], a[1][i], a[2][i], a[3][i]}, floatx4{a[4][i], a[5][i], a[6][i], a[7][i]}, ap);
+      split8(floatx4{a[0][i], a[1][i], a[2][i], a[3][i]}, floatx4{a[4][i], a[5][i], a[6][i], a[7][i]}, ap);
 #pragma unroll
       for (int t = 0; t < WB; ++t) {
-        if (ABL & 2) {
-          acc[i][t] += __builtin_bit_cast(floatx4, ap[0] ^ ap[1] ^ ap[2] ^ bp[t][0] ^ bp[t][1] ^ bp[t][2]);
-          continue;
-        }
         floatx4 c = acc[i][t];
         c = mfma_bf16(ap[2], bp[t][0], c);
         c = mfma_bf16(ap[1], bp[t][1], c);
@@ -1252,7 +1075,7 @@ __global__ __launch_bounds__(kThreads, D == 1 ? 4 : 1) void wgrad_x6_kernel(
   const int64_t g0 = p0 + 32 * wave;
   if (g0 < p1) {  // wave-uniform
     // values run D super-steps ahead, indices U = 2D ahead of their values (one VGPR per set)
-    constexpr int U = 2 * D;
+    constexpr int D = 2, U = 2 * D;
     Ix X[U];
     Vals V[D];
 #pragma unroll
@@ -1356,15 +1179,7 @@ PlanX6 plan_x6(int64_t n_rows, int c_out) {
   }
   p.n_y = n16 / p.nt;
   const int64_t blocks = n_tiles * p.n_y;
-  int64_t target = n_tiles <= 8 ? 2048 : 1024, cap = n_tiles <= 8 ? 16 : 8;
-#ifdef MSP_EXPERIMENTS  // split sweeps (scripts/kbench.py): MSP_X6D_SPLIT="target_small,cap_small,target,cap"
-  if (const char* e = getenv("MSP_X6D_SPLIT")) {
-    long v[4] = {2048, 16, 1024, 8};
-    sscanf(e, "%ld,%ld,%ld,%ld", &v[0], &v[1], &v[2], &v[3]);
-    target = n_tiles <= 8 ? v[0] : v[2];
-    cap = n_tiles <= 8 ? v[1] : v[3];
-  }
-#endif
+  const int64_t target = n_tiles <= 8 ? 2048 : 1024, cap = n_tiles <= 8 ? 16 : 8;
   if (blocks < target) {
     const int64_t sp = (target + blocks - 1) / blocks;
     p.split = (int)(sp > cap ? cap : sp);
@@ -1402,9 +1217,8 @@ int launch_x6(const PlanX6& p, const float* x, int c_in, const float* wt, int K,
   bool launched = false;
 #define LD(N, B)                                                                                              \
   if (!launched && p.nt == N && p.nb == B) {                                                                  \
-    conv_x6d_kernel<N, 32, 2, 128, 0, B><<<grid, kThreads, 0, s>>>(x, c_in, wsp, K, flip, c_out, tile_start,  \
-                                                                   chunk_off, chunk_src, chunk_row, n_rows,  \
-                                                                   p.n_y, p.split, dst);                     \
+    conv_x6d_kernel<N, B><<<grid, kThreads, 0, s>>>(x, c_in, wsp, K, flip, c_out, tile_start, chunk_off,      \
+                                                    chunk_src, chunk_row, n_rows, p.n_y, p.split, dst);      \
     launched = true;                                                                                          \
   }
   LD(4, 1) LD(4, 2) LD(3, 2) LD(2, 2) LD(1, 2)
@@ -1421,33 +1235,25 @@ int launch_x6(const PlanX6& p, const float* x, int c_in, const float* wt, int K,
   return MSP_OK;
 }
 
-#ifndef MSP_PAIRS_X6_FORM
-#define MSP_PAIRS_X6_FORM 2  // runs with the weights in registers: profiles/r06/pairs_bench_r06pb.log
-#endif
-
-// form % 10: 0 one chunk per wave, 1 runs of chunks (c_in <= 128), 2 runs with the weights in registers; form / 10:
-// the waves the runs are sized for (x 1024; 0 = 8192)
-void launch_pairs_x6(int form, const float* x, int c_in, const u32x4* img, int K, int c_out, const int32_t* pair_in,
+// Runs of chunks sized for 8192 waves, with the weights in registers (c_in <= 128; one chunk per wave above):
+// profiles/r06/pairs_bench_r06pb.log
+void launch_pairs_x6(const float* x, int c_in, const u32x4* img, int K, int c_out, const int32_t* pair_in,
                      const int32_t* pair_out, const int64_t* off_start, const int64_t* chunk_start, int64_t n_chunks,
                      float* out, hipStream_t s) {
   const int NT = (c_out / 16) % 2 == 0 ? 2 : 1, n_y = c_out / (16 * NT);
-  const int kind = form % 10;
-  if (kind != 0 && c_in <= 128) {
-    const int64_t waves = form / 10 ? (int64_t)(form / 10) * 1024 : 8192;
-    int64_t run = n_chunks * n_y / waves;
+  if (c_in <= 128) {
+    int64_t run = n_chunks * n_y / 8192;
     run = run < 1 ? 1 : run > 16 ? 16 : run;
     dim3 grid((unsigned)ceil_div(ceil_div(n_chunks, run), kWaves), (unsigned)n_y);
-#define PIPE(N, KK, WR)                                                                                          \
-  conv_pairs_x6_pipe_kernel<N, KK, WR><<<grid, kThreads, 0, s>>>(x, c_in, img, K, c_out, pair_in, pair_out,     \
-                                                                off_start, chunk_start, n_chunks, (int)run, n_y, \
-                                                                out)
-    const bool wr = kind == 2;
+#define PIPE(N, KK)                                                                                              \
+  conv_pairs_x6_pipe_kernel<N, KK><<<grid, kThreads, 0, s>>>(x, c_in, img, K, c_out, pair_in, pair_out,          \
+                                                             off_start, chunk_start, n_chunks, (int)run, n_y, out)
     if (c_in <= 64) {
-      if (NT == 2) { if (wr) PIPE(2, 2, true); else PIPE(2, 2, false); }
-      else { if (wr) PIPE(1, 2, true); else PIPE(1, 2, false); }
+      if (NT == 2) PIPE(2, 2);
+      else PIPE(1, 2);
     } else {
-      if (NT == 2) { if (wr) PIPE(2, 4, true); else PIPE(2, 4, false); }
-      else { if (wr) PIPE(1, 4, true); else PIPE(1, 4, false); }
+      if (NT == 2) PIPE(2, 4);
+      else PIPE(1, 4);
     }
 #undef PIPE
     return;
@@ -1484,7 +1290,7 @@ int msp_conv_pairs_x6(const float* x, int c_in, const float* wt, int K, int c_ou
   u32x4* img = static_cast<u32x4*>(ws);
   const int64_t units = (int64_t)msp_conv_pairs_x6_workspace_size(K, c_in, c_out) / 16;
   split_weights_kernel<<<(unsigned)ceil_div(units, 256), 256, 0, s>>>(wt, K, c_out, c_in, NC, 32, img, 0);
-  launch_pairs_x6(MSP_PAIRS_X6_FORM, x, c_in, img, K, c_out, pair_in, pair_out, off_start, chunk_start, n_chunks,
+  launch_pairs_x6(x, c_in, img, K, c_out, pair_in, pair_out, off_start, chunk_start, n_chunks,
                   out, s);
   return check_launch("msp_conv_pairs_x6");
 }
@@ -1496,12 +1302,9 @@ int msp_conv_pairs_x6(const float* x, int c_in, const float* wt, int K, int c_ou
 // dense row order, ~0.4 ms of side-stream build per step (a 5-pass radix sort and a permuted copy of the 27 x V
 // map), and the per-wave tiles, whose rulebook level 0 builds anyway, now run the call as fast: 50.35-50.42 vs
 // 50.43-50.52 ms/step (profiles/r05/ab_r05ag_no_nbr.log).  The kernel stays (msp_conv_nbr, tested directly).
-#ifndef MSP_NBR_FORM  // experiments: 1 = the round-1..4 routing above
-#define MSP_NBR_FORM 0
-#endif
 int msp_conv_nbr_preferred(int64_t n_rows, int c_in, int c_out) {
-  (void)c_in;
-  return MSP_NBR_FORM && n_rows >= 100000 && c_out >= 64 && c_out % 16 == 0 ? 1 : 0;
+  (void)n_rows, (void)c_in, (void)c_out;
+  return 0;
 }
 
 size_t msp_conv_nbr_workspace_size(int K, int c_in, int c_out) {
@@ -1523,36 +1326,5 @@ int msp_conv_nbr(const float* x, int c_in, const float* wt, int K, int flip, int
   const int rc = launch_x6g(x, c_in, wt, K, flip, c_out, nbr, perm, n_rows, out, ws, as_stream(stream));
   return rc ? rc : check_launch("msp_conv_nbr");
 }
-
-#ifdef MSP_EXPERIMENTS
-int msp_exp_conv_pairs_x6(int variant, const float* x, int c_in, const float* wt, int K, int c_out,
-                          const int32_t* pair_in, const int32_t* pair_out, const int64_t* off_start,
-                          const int64_t* chunk_start, int64_t n_chunks, float* out, void* ws, size_t ws_bytes,
-                          msp_stream_t stream) {
-  MSP_REQUIRE(c_in > 0 && c_in % 16 == 0 && c_out > 0 && c_out % 16 == 0 && K >= 1, "msp_exp_conv_pairs_x6: shape");
-  MSP_REQUIRE(ws && ws_bytes >= msp_conv_pairs_x6_workspace_size(K, c_in, c_out), "msp_exp_conv_pairs_x6: ws");
-  if (n_chunks == 0) return MSP_OK;
-  hipStream_t s = as_stream(stream);
-  const int NT = (c_out / 16) % 2 == 0 ? 2 : 1;
-  u32x4* img = static_cast<u32x4*>(ws);
-  const int64_t units = (int64_t)msp_conv_pairs_x6_workspace_size(K, c_in, c_out) / 16;
-  split_weights_kernel<<<(unsigned)ceil_div(units, 256), 256, 0, s>>>(wt, K, c_out, c_in, 16 * NT, 32, img, 0);
-  launch_pairs_x6(variant, x, c_in, img, K, c_out, pair_in, pair_out, off_start, chunk_start, n_chunks, out, s);
-  return check_launch("msp_exp_conv_pairs_x6");
-}
-
-int msp_exp_conv_x6r(int variant, const float* x, int c_in, const float* wt, int K, int flip, int c_out,
-                     int tile_rows, const int64_t* tile_start, const uint8_t* chunk_off, const int32_t* chunk_src,
-                     const uint16_t* chunk_row, int64_t n_rows, float* out, void* ws, size_t ws_bytes,
-                     msp_stream_t stream) {
-  MSP_REQUIRE(c_out <= 32 && c_in <= 64 && c_in % 16 == 0 && c_out % 16 == 0, "msp_exp_conv_x6r: shape");
-  const size_t need = x6p_ws_bytes(K, c_in, c_out) + 1024 + (variant >= 100 ? (size_t)n_rows * c_in * 6 : 0);
-  MSP_REQUIRE(ws && ws_bytes >= need, "msp_exp_conv_x6r: workspace");
-  if (n_rows <= 0) return MSP_OK;
-  const int rc = launch_x6r_exp(variant, x, c_in, wt, K, flip, c_out, tile_rows, tile_start, chunk_off, chunk_src,
-                                chunk_row, n_rows, out, ws, as_stream(stream));
-  return rc ? rc : check_launch("msp_exp_conv_x6r");
-}
-#endif
 
 }  // extern "C"

@@ -31,8 +31,6 @@
 // msp_conv_x6.hip, six piece products summed in a zeroed accumulator and added
 // once).  The four waves' partial sums are added in wave order through LDS at
 // the end (deterministic).  Input channels are staged 32 at a time.
-#include <type_traits>
-
 #include "msp_x6.h"
 #include "msp_bn_epi.h"
 
@@ -66,22 +64,19 @@ __device__ void bitonic_i32(int32_t* a) {
 }
 
 // The tile's distinct input rows, unordered: its K x T neighbour entries (all loads in flight first) go
-// into an open-addressing hash set in LDS (kHashMult N2 int32 slots, linear probing by LDS CAS); each first
+// into an open-addressing hash set in LDS (N2 int32 slots, linear probing by LDS CAS); each first
 // insertion appends the row to uq.  Returns the count.  (Round 2 replaced a bitonic sort of all N2 entries: a
 // tile names 1.6-2 x T distinct rows of 27 T entries, so sorting only those is ~10x less work.)  Slots: N2 since
 // round 5 (load 0.05-0.1 on surfaces, at most 0.84 for a map whose 27 T entries are all distinct): 32 KB of LDS per
 // block instead of 48, so a build block beside the compute stream's one-block-per-CU weight gradient (125 KB) no
 // longer keeps it off that CU.
-#ifndef MSP_LOCAL_HASH_MULT  // experiments: 2 = the round-2..4 table (2 N2 slots)
-#define MSP_LOCAL_HASH_MULT 1
-#endif
 template <int T, int N2>
 __device__ int tile_distinct(const int32_t* __restrict__ nbr, int K, int64_t n, int64_t t, int32_t* h, int32_t* uq,
                              int* cnt, int32_t (&m)[N2 / kLT], uint32_t* msk = nullptr) {
   // m: this thread's entries (offset i / T, row i % T for i = threadIdx.x + kLT j; -1 absent), kept in registers
   // for the caller (the fill's local indices).  msk (optional, T words): each row's neighbour mask, set here from
   // those same entries by LDS OR.
-  constexpr int HS = MSP_LOCAL_HASH_MULT * N2, HB = __builtin_ctz(HS);
+  constexpr int HS = N2, HB = __builtin_ctz(HS);
   constexpr int PER = N2 / kLT;  // K T <= N2 entries
   for (int i = threadIdx.x; i < HS; i += kLT) h[i] = -1;
   if (msk)
@@ -152,7 +147,7 @@ __device__ void bitonic_i32_n(int32_t* a, int n2) {
 template <int T, int N2>
 __global__ __launch_bounds__(kLT) void local_count_kernel(const int32_t* __restrict__ nbr, int K, int64_t n,
                                                           int64_t* __restrict__ cnt) {
-  __shared__ int32_t h[MSP_LOCAL_HASH_MULT * N2];
+  __shared__ int32_t h[N2];
   __shared__ int32_t uq[N2];
   __shared__ int c;
   const int64_t t = blockIdx.x;
@@ -230,9 +225,6 @@ __device__ void group_rows(const uint32_t* __restrict__ msk, int nv, uint8_t* __
 // = 4 x groups + 1 per offset; at most 8 offsets a wave).  Interleaving the halves over the groups evens them
 // out, and the lists even out the waves: the slowest of the 8 waves carries 0.94 of the mean against 0.86 for
 // offsets dealt round-robin (headline batch, levels 1-3).  wo[h][c][k]: offset k of wave c (0xFF: none).
-#ifndef MSP_SHARED_LISTS  // experiments: 1 = both halves walk one list dealt from all 8 groups (their weight loads
-#define MSP_SHARED_LISTS 0  // then coincide, which the vector L1 can serve once)
-#endif
 // One wave deals both halves: lanes 32 h + o hold offset o's cost in half h; each lane ranks its offset (cost
 // descending, then offset ascending: the order an insertion sort by cost gives) with K shuffles, the ranked lists
 // go to LDS, and lanes 0 and 32 deal them out greedily from registers.  (Round 4's form ran the ranking as an
@@ -242,7 +234,7 @@ __device__ void deal_offsets(const uint32_t* __restrict__ gmask, int K, uint8_t*
   const int lane = threadIdx.x & 63, h = lane >> 5, o = lane & 31;
   int a = 0;  // item / cost: [2][kKMax] LDS scratch; wo2: the tile's two halves' lists (2 x 32 bytes)
   if (o < K)
-    for (int g = MSP_SHARED_LISTS ? 0 : h; g < 8; g += MSP_SHARED_LISTS ? 1 : 2) a += (gmask[g] >> o) & 1u;
+    for (int g = h; g < 8; g += 2) a += (gmask[g] >> o) & 1u;
   int r = 0;
   for (int q = 0; q < K; ++q) {
     const int aq = __shfl(a, (h << 5) + q, 64);
@@ -330,7 +322,7 @@ __global__ __launch_bounds__(kLT) void local_fill_kernel(const int32_t* __restri
                                                          int64_t n_pad, const int64_t* __restrict__ u_start,
                                                          int32_t* __restrict__ u_rows, uint16_t* __restrict__ lidx,
                                                          int32_t* __restrict__ perm, uint8_t* __restrict__ wave_off) {
-  constexpr int HS = MSP_LOCAL_HASH_MULT * N2;
+  constexpr int HS = N2;
   __shared__ int32_t h[HS];
   __shared__ int32_t uq[N2];
   __shared__ uint8_t iord[MODE ? T : 1];  // where tile row p goes in the chosen order
@@ -463,18 +455,16 @@ __device__ __forceinline__ int xs_unit(int j, int p, int qq) { return j * kXU + 
 // wave-uniform masks of the groups with the offset and with rows past the staged capacity, and per active
 // group issues three LDS reads and 6 NT MFMAs.  Weight fragments come from the lane-ordered image one offset
 // ahead.  The four waves' partial sums of a half are added in wave order through LDS at the end (deterministic).
-// AB (experiments build only; wrong results): bit 0 stages without the global value loads, bit 2 keeps the
-// first offset's weight fragments, bit 3 reads staged row 16 g + r for every present rule (16 distinct j mod 16 per
-// lane group: no bank conflict) -- the ablations that price the staging, weight-load and LDS-conflict costs.
-// AC (accumulation): 1 = the six piece products of a step go straight into the group's running sums, smallest
-// first (the product form); 0 = summed in a zeroed accumulator and added with a vector add (round 2-3 form:
-// about a third of the rounding error, 6-9 % slower -- profiles/r03/kbexp_r03x_accumulate.log).
-// WB (weight fragment register sets): 1 = one set, the next step's fragments loaded after the step's MFMAs (their
-// latency exposed at the next step's start); 2 = two sets alternating, the next step's fragments loaded before the
-// step's MFMAs, so a whole step hides their latency (the first step of each slice loads after the staging).
+// The six piece products of a step go straight into the group's running sums, smallest first (summing them in a
+// zeroed accumulator first, the round 2-3 form, was 6-9 % slower: profiles/r03/kbexp_r03x_accumulate.log), and one
+// set of weight fragment registers is loaded after the step's MFMAs (a second, alternating set lost in round 4:
+// DESIGN.md §3.8).
+// AB (experiments build only; wrong results): bit 0 stages without the global value loads, bit 3 reads staged row
+// 16 g + r for every present rule (16 distinct j mod 16 per lane group: no bank conflict) -- the ablations that
+// price the staging and LDS-conflict costs.
 // EPI (msp_bn_epilogue, round 6): the BatchNorm sums of the rows written; its own instantiation, so the plain form
 // compiles exactly as before (the epilogue's registers and loads never touch it).
-template <int NT, int AB = 0, int AC = 1, int WB = 1, bool EPI = false>
+template <int NT, int AB = 0, bool EPI = false>
 __global__ __launch_bounds__(512, 4) void conv_x6s_kernel(
     const float* __restrict__ x, int c_in, const u32x4* __restrict__ wimg, int K, int flip, int c_out,
     const uint16_t* __restrict__ lidx, const int64_t* __restrict__ u_start, const int32_t* __restrict__ u_rows,
@@ -551,16 +541,6 @@ __global__ __launch_bounds__(512, 4) void conv_x6s_kernel(
     const int ks = sc / n_j, j = sc - ks * n_j;
     const int o = off_of(j);
     const int ow = flip ? K - 1 - o : o;
-    if constexpr (WB == 2) {  // wave-uniform row base (scalar registers) + the lane's 32-bit byte offset
-      const u32x4* src = wimg + ((((int64_t)ow * n_y + cy) * nks + ks) * NT) * 3 * 64;
-      const char* b = reinterpret_cast<const char*>(src);
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-          w[t][p] = *reinterpret_cast<const u32x4*>(b + (uint32_t)(((t * 3 + p) * 64 + lane) * 16));
-      return;
-    }
     const u32x4* src = wimg + ((((int64_t)ow * n_y + cy) * nks + ks) * NT) * 3 * 64 + lane;
 #pragma unroll
     for (int t = 0; t < NT; ++t)
@@ -581,9 +561,6 @@ __global__ __launch_bounds__(512, 4) void conv_x6s_kernel(
     floatx4 v[MI][2];
 #pragma unroll
     for (int b = 0; b < MI; ++b) {
-      // WB 2: the row addresses are formed here, per slice (hoisted out of the slice loop they hold 6 registers
-      // for the whole kernel, which the second weight set needs)
-      if constexpr (WB == 2) asm volatile("" : "+v"(srow[b]));
       const int i = tid + NTH * b;
       const int k = k0 + 8 * (i & 3);
       v[b][0] = v[b][1] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -608,8 +585,8 @@ __global__ __launch_bounds__(512, 4) void conv_x6s_kernel(
       }
     }
   };
-  // one (k-slice, offset) step of this wave over its row groups; FAR: the tile lists rows past the staged capacity
-  auto run = [&](int ks, int o, const u32x4 (&w)[NT][3], auto FAR) {
+  // one (k-slice, offset) step of this wave over its row groups (far: groups listing rows past the staged capacity)
+  auto run = [&](int ks, int o, const u32x4 (&w)[NT][3]) {
     const uint16_t* lo = ls + o * T + 16 * rp + r;
     int li[G];
 #pragma unroll
@@ -619,7 +596,7 @@ __global__ __launch_bounds__(512, 4) void conv_x6s_kernel(
     for (int g = 0; g < G; ++g) {
       const bool pres = li[g] != kAbsent;
       act |= (ballot64(pres) != 0 ? 1u : 0u) << g;
-      if constexpr (decltype(FAR)::value) far |= (ballot64(pres && li[g] >= kUCap) != 0 ? 1u : 0u) << g;
+      far |= (ballot64(pres && li[g] >= kUCap) != 0 ? 1u : 0u) << g;
     }
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -629,7 +606,7 @@ __global__ __launch_bounds__(512, 4) void conv_x6s_kernel(
         if constexpr ((AB & 8) != 0) jr = li[g] < kUCap ? 16 * g + r : kUCap;  // ablation: conflict-free reads
 #pragma unroll
         for (int p = 0; p < 3; ++p) cur[p] = xs[xs_unit(jr, p, q)];
-        if (decltype(FAR)::value && ((far >> g) & 1)) {  // rows past the staged capacity: from global memory (rare)
+        if ((far >> g) & 1) {  // rows past the staged capacity: from global memory (rare)
           const bool f = li[g] != kAbsent && li[g] >= kUCap;
           const int k = 32 * ks + 8 * q;
           floatx4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
@@ -643,36 +620,19 @@ __global__ __launch_bounds__(512, 4) void conv_x6s_kernel(
 #pragma unroll
           for (int p = 0; p < 3; ++p) cur[p] = f ? fp[p] : cur[p];
         }
-        if constexpr (AC == 1) {  // smallest products first, straight into the running sums
+        // smallest products first, straight into the running sums
 #pragma unroll
-          for (int t = 0; t < NT; ++t) acc[g][t] = mfma_bf16(w[t][2], cur[0], acc[g][t]);
+        for (int t = 0; t < NT; ++t) acc[g][t] = mfma_bf16(w[t][2], cur[0], acc[g][t]);
 #pragma unroll
-          for (int t = 0; t < NT; ++t) acc[g][t] = mfma_bf16(w[t][1], cur[1], acc[g][t]);
+        for (int t = 0; t < NT; ++t) acc[g][t] = mfma_bf16(w[t][1], cur[1], acc[g][t]);
 #pragma unroll
-          for (int t = 0; t < NT; ++t) acc[g][t] = mfma_bf16(w[t][0], cur[2], acc[g][t]);
+        for (int t = 0; t < NT; ++t) acc[g][t] = mfma_bf16(w[t][0], cur[2], acc[g][t]);
 #pragma unroll
-          for (int t = 0; t < NT; ++t) acc[g][t] = mfma_bf16(w[t][1], cur[0], acc[g][t]);
+        for (int t = 0; t < NT; ++t) acc[g][t] = mfma_bf16(w[t][1], cur[0], acc[g][t]);
 #pragma unroll
-          for (int t = 0; t < NT; ++t) acc[g][t] = mfma_bf16(w[t][0], cur[1], acc[g][t]);
+        for (int t = 0; t < NT; ++t) acc[g][t] = mfma_bf16(w[t][0], cur[1], acc[g][t]);
 #pragma unroll
-          for (int t = 0; t < NT; ++t) acc[g][t] = mfma_bf16(w[t][0], cur[0], acc[g][t]);
-        } else {
-          floatx4 c[NT];
-#pragma unroll
-          for (int t = 0; t < NT; ++t) c[t] = mfma_bf16(w[t][2], cur[0], floatx4{0.f, 0.f, 0.f, 0.f});
-#pragma unroll
-          for (int t = 0; t < NT; ++t) c[t] = mfma_bf16(w[t][1], cur[1], c[t]);
-#pragma unroll
-          for (int t = 0; t < NT; ++t) c[t] = mfma_bf16(w[t][0], cur[2], c[t]);
-#pragma unroll
-          for (int t = 0; t < NT; ++t) c[t] = mfma_bf16(w[t][1], cur[0], c[t]);
-#pragma unroll
-          for (int t = 0; t < NT; ++t) c[t] = mfma_bf16(w[t][0], cur[1], c[t]);
-#pragma unroll
-          for (int t = 0; t < NT; ++t) c[t] = mfma_bf16(w[t][0], cur[0], c[t]);
-#pragma unroll
-          for (int t = 0; t < NT; ++t) acc[g][t] += c[t];
-        }
+        for (int t = 0; t < NT; ++t) acc[g][t] = mfma_bf16(w[t][0], cur[0], acc[g][t]);
       }
     }
   };
@@ -696,45 +656,16 @@ __global__ __launch_bounds__(512, 4) void conv_x6s_kernel(
     }
   };
 
-  using Far = std::true_type;
-  using Near = std::false_type;
-  if (WB == 2 && U <= kUCap) {  // block-uniform: every listed row is staged (all but 0-0.09 % of tiles)
-    // Two fragment sets: step j of a slice runs on set j & 1 while the next step's fragments load into the other.
-    // The step loop has a fixed trip count of 8 (the longest offset list) and is unrolled, with every load
-    // unconditional (steps past the list reload a valid step; the last one of a slice loads the next slice's
-    // first), so the compiler's in-order load count waits only for the older set at each step's first MFMA --
-    // data-dependent branches around the loads would leave a vmcnt(0) there instead.
-    u32x4 wa[NT][3], wb[NT][3];
-    auto ld_next = [&](int ks, int j, u32x4 (&w)[NT][3]) {  // fragments of the step after (ks, j)
-      const int s1 = j + 1 < n_j ? ks * n_j + j + 1 : (ks + 1 < nks ? (ks + 1) * n_j : ks * n_j + n_j - 1);
-      ld_w(s1, w);
-    };
-    if (n_j) ld_w(0, wa);
-    for (int ks = 0; ks < nks; ++ks) {
-      if (ks) __syncthreads();  // previous slice's readers done
-      stage(ks);
-      __syncthreads();
-      if (ks == nks - 1) epi_prefetch();
-#pragma unroll
-      for (int j = 0; j < 8; j += 2) {
-        ld_next(ks, j, wb);
-        if (j < n_j) run(ks, off_of(j), wa, Near{});
-        ld_next(ks, j + 1, wa);
-        if (j + 1 < n_j) run(ks, off_of(j + 1), wb, Near{});
-      }
-    }
-  } else {
-    u32x4 wf[NT][3];
-    if (n_j) ld_w(0, wf);
-    for (int ks = 0; ks < nks; ++ks) {
-      if (ks) __syncthreads();  // previous slice's readers done
-      stage(ks);
-      __syncthreads();
-      if (ks == nks - 1) epi_prefetch();
-      for (int j = 0; j < n_j; ++j) {
-        run(ks, off_of(j), wf, Far{});
-        if constexpr (!(AB & 4)) ld_w(ks * n_j + j + 1, wf);
-      }
+  u32x4 wf[NT][3];
+  if (n_j) ld_w(0, wf);
+  for (int ks = 0; ks < nks; ++ks) {
+    if (ks) __syncthreads();  // previous slice's readers done
+    stage(ks);
+    __syncthreads();
+    if (ks == nks - 1) epi_prefetch();
+    for (int j = 0; j < n_j; ++j) {
+      run(ks, off_of(j), wf);
+      ld_w(ks * n_j + j + 1, wf);
     }
   }
   // the four waves' partial sums of each half, added in wave order
@@ -832,8 +763,8 @@ __global__ __launch_bounds__(256) void wgrad_ranges_reduce_kernel(const floatx4*
 // The pair-list form (wgrad_x6_kernel) gathers x and dy per rule from L2/MALL (7-8x the compulsory bytes at
 // levels 0-1) and splits every gathered value per use; the dense tile-local form (wgrad_x6t_kernel) staged
 // the rows once but ran 32-row k-steps with ~45 % zero rows.  Here a tile's distinct x rows and its 128 dy rows
-// are staged in LDS once per 32 x 32 channel slice as three bf16 piece images ([row][32 channels], 8-byte
-// units XOR-spread by row bit 2), and the k-steps are the compacted chunks of the rulebook: two 16-rule chunks
+// are staged in LDS once per 32 x 32 channel slice as three bf16 piece images ([row][32 channels], rows
+// padded to 72 bytes), and the k-steps are the compacted chunks of the rulebook: two 16-rule chunks
 // of one offset per 32-deep MFMA step (an odd last chunk is paired with the zero row).  The MFMA operands
 // (A = x^T, B = dy^T: 8 consecutive rules of one channel per lane) come straight out of the gathered rows with
 // the transposing LDS read ds_read_b64_tr_b16: lane 4 qq + p of a 16-lane group names rule qq's row and its
@@ -842,10 +773,9 @@ __global__ __launch_bounds__(256) void wgrad_ranges_reduce_kernel(const floatx4*
 // w, w + 8, w + 16, w + 24 and keeps their 32 x 32 tiles in registers over the range; the next tile's rows,
 // values and rule words are in flight in registers while the current tile computes.  Per range a slab of
 // partial dW is written and the ranges are added in order (deterministic).
-#ifndef MSP_X6C_CAP  // experiments: 384 keeps the block (with 72-byte rows) + one 32 KB build block within a CU's LDS
-#define MSP_X6C_CAP 448
-#endif
-constexpr int kWCap = MSP_X6C_CAP;  // distinct rows per 128-row tile the weight gradient stages (msp_conv_wgrad_chunk)
+// distinct rows per 128-row tile the weight gradient stages (msp_conv_wgrad_chunk); 384, which keeps the block and
+// one 32 KB build block within a CU's LDS, measured no faster (profiles/r05/ab_r05r_x6c_cap384.log)
+constexpr int kWCap = 448;
 constexpr uint32_t kWFar = 0xFFFFu;  // chunk entry whose input row lies past kWCap (never staged)
 
 constexpr int kWTile = 128;
@@ -1035,19 +965,12 @@ constexpr int kWMaxCh = 216;                   // chunks of one 128-row tile (K 
 __device__ __constant__ const uint32_t kX6cDeal[8] = {0x1a150a06u, 0x19141103u, 0x120f0502u, 0xff130c01u,
                                                       0xff090704u, 0xffff0e0du, 0xff161000u, 0x18170b08u};
 
+// Row stride of the piece images, bf16 elements: rows padded to 72 bytes, unswizzled, so the 16 rows one transposing
+// read names start at 8-byte granules spread over the banks (the round 2-4 XOR-swizzled 64-byte rows were 9-15 %
+// slower at every level: DESIGN.md §3.8, profiles/r05/kbexp_r05m_x6c_row_stride.log).
+constexpr int kWRS = 36;
 // bf16 element offset of 8-byte unit v (channels 4v .. 4v+3 of the slice) of row j in a piece image
-__device__ __forceinline__ int wimg_off(int j, int v) { return j * 32 + 4 * (v ^ (((j >> 2) & 1) << 2)); }
-// RS (row stride of the piece images, bf16 elements): 32 = the XOR-swizzled layout above; 36 = rows padded to 72
-// bytes, unswizzled, so the 16 rows one transposing read names start at 8-byte granules spread over the banks instead
-// of eight 32-byte windows (experiments: the round-4 PMC put bank conflicts at 0.42 of the kernel's LDS cycles)
-#ifndef MSP_X6C_RS  // the product's image row stride (experiments: 32 = the round-2..4 swizzled rows)
-#define MSP_X6C_RS 36
-#endif
-template <int RS>
-__device__ __forceinline__ int wimg_off_rs(int j, int v) {
-  if constexpr (RS == 32) return wimg_off(j, v);
-  return j * RS + 4 * v;
-}
+__device__ __forceinline__ int wimg_off(int j, int v) { return j * kWRS + 4 * v; }
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint2 tr_read(const uint16_t* p) {
@@ -1073,52 +996,49 @@ __device__ __forceinline__ void split4(const floatx4& a, uint2 (&p)[3]) {
   }
 }
 
-// AC as conv_x6s: 1 (the product form) accumulates the six piece products straight into the running tile sums,
-// 0 sums each step in a zeroed accumulator first (12-16 % slower, profiles/r03/kbexp_r03x_accumulate.log).
-// PW 1 (the product form): the next k-step's rule words are read from LDS at the start of the current one (within
-// an offset), so a k-step no longer opens with an LDS read -> address -> transposing-read chain: 1-6 % faster at
-// levels 0-3 (profiles/r03/kbexp_r03pw.log); PW 0 reads them at the k-step's start.
-// ABL (experiments build only; wrong results): bit 0 keeps the first tile's LDS images for every tile (no split and
-// no image writes after the first tile; the rule words and offsets are still staged), bit 1 drops the next tile's
-// value loads -- the ablations that price the per-tile staging (round 6: -20 %, profiles/r06/kbexp_r06m_x6c_staging.log).
-// DT 1 (direct offset table, the product since round 6): each chunk's neighbours' offsets come with its own from
-// global memory, so the table of the offsets' chunk ranges is written in the same phase as the images
-// (double-buffered, the idle buffer zeroed there): one block barrier per tile instead of two, 7-15 % faster at
-// levels 0-3 (profiles/r06/kbexp_r06o_x6c_table_balance_split.log).  DT 0: the table built through LDS after the
-// images (round 2-5).  Measured there and not kept: splitting the next tile's values in registers before the
-// barrier (38 VGPRs past the 256 two waves per SIMD allow: spills, 20-40 % slower) and dealing the offsets over the
-// waves by the range's chunk counts (no gain: -2 % to +8 %).
-// BR > 0 (balanced ranges): the blocks' contiguous tile ranges hold equal cost, chunks + BR per tile (the staging's
-// share), instead of equal tile counts; each block finds its bounds in tile_start (a prefix sum of chunks) with two
-// rounds of block-wide counts.  Still a fixed function of the index: deterministic.  The product runs BR = 128:
-// against equal tile counts 2-4 % faster at levels 0-1, 8 % at level 2, 10-12 % at level 3, 3-6 % at level 4 (the
-// few-tile levels' ranges of 17 or 18 tiles differed by a tile; profiles/r06/kbexp_r06{q,r}_x6c_balanced_ranges.log).
-// DL 1 (offset deal table, NW = 8): wave w owns the offsets of kX6cDeal[w] instead of w, w + 8, ...  Every tile
+// The six piece products accumulate straight into the running tile sums (summed in a zeroed accumulator first:
+// 12-16 % slower, profiles/r03/kbexp_r03x_accumulate.log).  The next k-step's rule words are read from LDS at the
+// start of the current one (within an offset), so a k-step no longer opens with an LDS read -> address ->
+// transposing-read chain: 1-6 % faster at levels 0-3 than reading them at the k-step's start
+// (profiles/r03/kbexp_r03pw.log).  Pricing the per-tile staging by ablation: -20 %
+// (profiles/r06/kbexp_r06m_x6c_staging.log).
+// Direct offset table (since round 6): each chunk's neighbours' offsets come with its own from global memory, so the
+// table of the offsets' chunk ranges is written in the same phase as the images (double-buffered, the idle buffer
+// zeroed there): one block barrier per tile instead of the two of the round 2-5 table built through LDS after the
+// images, 7-15 % faster at levels 0-3 (profiles/r06/kbexp_r06o_x6c_table_balance_split.log).  Measured there and not
+// kept: splitting the next tile's values in registers before the barrier (38 VGPRs past the 256 two waves per SIMD
+// allow: spills, 20-40 % slower) and dealing the offsets over the waves by the range's chunk counts (no gain: -2 %
+// to +8 %).
+// Balanced ranges: the blocks' contiguous tile ranges hold equal cost, chunks + kWBR per tile (the staging's share),
+// instead of equal tile counts; each block finds its bounds in tile_start (a prefix sum of chunks) with two rounds
+// of block-wide counts.  Still a fixed function of the index: deterministic.  Against equal tile counts 2-4 % faster
+// at levels 0-1, 8 % at level 2, 10-12 % at level 3, 3-6 % at level 4 (the few-tile levels' ranges of 17 or 18 tiles
+// differed by a tile; profiles/r06/kbexp_r06{q,r}_x6c_balanced_ranges.log).
+// DL 1 (offset deal table): wave w owns the offsets of kX6cDeal[w] instead of w, w + 8, ...  Every tile
 // waits at its barrier for its slowest wave, and on surfaces the round-robin deal stacks one plane's heavy offsets
 // on a few waves: the slowest wave carries 1.38 / 1.31 / 1.28 / 1.24 / 1.21 x the mean k-steps at levels 0-4 of the
 // headline batch.  The table was chosen offline by local search over those per-tile counts (scripts/kbench.py
 // X6C_DUMP; weighted by each level's share of the step): 1.18 / 1.17 / 1.16 / 1.17 / 1.17 x, and fitted on levels
 // 0-1 alone it gives the held-out levels 2-4 the same 1.17 -- it follows the scenes' axis-aligned planes, not the
 // batch.  An offset's sums are the same k-steps in the same order whichever wave runs them: bit-identical.
-template <int NW, int AC = 1, int PW = 1, int RS = 32, int ABL = 0, int DT = 0, int BR = 0, int DL = 0>
-__global__ __launch_bounds__(64 * NW, 1) void wgrad_x6c_kernel(
+constexpr int kWBR = 128;  // a tile's staging, in chunks, in the cost the ranges balance
+template <bool DL>
+__global__ __launch_bounds__(512, 1) void wgrad_x6c_kernel(
     const float* __restrict__ x, int c_in, const float* __restrict__ dy, int c_out, int K,
     const int64_t* __restrict__ tile_start, const uint8_t* __restrict__ chunk_off,
     const uint32_t* __restrict__ chunk_lr, const int64_t* __restrict__ u_start, const int32_t* __restrict__ u_rows,
     int64_t n_rows, int64_t n_tiles, int n_ranges, float* __restrict__ slab) {
-  constexpr int NTH = 64 * NW, NOW = 32 / NW;          // offsets per wave: o = wave + NW a, a < NOW (DL: the table)
-  static_assert(!DL || NW == 8, "the offset deal table is for 8 waves");
+  constexpr int NW = 8, NTH = 64 * NW, NOW = 32 / NW;  // offsets per wave: o = wave + NW a, a < NOW (DL: the table)
   constexpr int XI = (kWCap * 8 + NTH - 1) / NTH;     // x staging items (row, 4 channels) per thread
   constexpr int DI = kWTile * 8 / NTH;                // dy staging items per thread
   constexpr int EI = (kWMaxCh * 16 + NTH - 1) / NTH;  // rule words per thread
   static_assert(DI * NTH == kWTile * 8, "dy staging items must divide evenly");
   // bf16 elements of one x piece image (+ zero row kWCap) and of one dy piece image (+ zero row 128)
-  constexpr int kWXImg = (kWCap + 1) * RS, kWDImg = (kWTile + 1) * RS;
+  constexpr int kWXImg = (kWCap + 1) * kWRS, kWDImg = (kWTile + 1) * kWRS;
   __shared__ __attribute__((aligned(16))) uint16_t xim[3 * kWXImg];
   __shared__ __attribute__((aligned(16))) uint16_t dim[3 * kWDImg];
   __shared__ uint32_t ent[(kWMaxCh + 1) * 16];  // + one chunk: the partner read of a last odd chunk stays inside
-  __shared__ uint8_t offs[kWMaxCh];
-  __shared__ int otab[2][2][32];  // [buffer][first, end][offset]; DT 0: buffer 0 only
+  __shared__ int otab[2][2][32];  // [buffer][first, end][offset]
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int g = lane >> 4, i16 = lane & 15, qq = i16 >> 2, p4 = i16 & 3;
@@ -1130,42 +1050,40 @@ __global__ __launch_bounds__(64 * NW, 1) void wgrad_x6c_kernel(
   const int range = (int)(lb / n_slices);
   const int ci0 = 32 * (slice / n_sl_o), co0 = 32 * (slice % n_sl_o);
   int64_t t0 = (int64_t)range * n_tiles / n_ranges, t1 = (int64_t)(range + 1) * n_tiles / n_ranges;
-  if constexpr (BR > 0) {
-    if (n_tiles <= (int64_t)NTH * NTH) {  // block-uniform
-      __shared__ int bcnt[2][2][NW];
-      auto cost = [&](int64_t t) { return tile_start[t] + (int64_t)BR * t; };
-      const int64_t c0 = cost(0), total = cost(n_tiles) - c0;
-      const int64_t tg[2] = {c0 + (int64_t)range * total / n_ranges, c0 + (int64_t)(range + 1) * total / n_ranges};
-      // bound(tg) = the first tile of cost >= tg (cost is increasing): round 0 counts the samples t = i st below
-      // each target, round 1 the tiles of the interval that leaves
-      const int64_t st = (n_tiles + NTH - 1) / NTH;
-      int64_t base[2] = {0, 0};
+  if (n_tiles <= (int64_t)NTH * NTH) {  // block-uniform
+    __shared__ int bcnt[2][2][NW];
+    auto cost = [&](int64_t t) { return tile_start[t] + (int64_t)kWBR * t; };
+    const int64_t c0 = cost(0), total = cost(n_tiles) - c0;
+    const int64_t tg[2] = {c0 + (int64_t)range * total / n_ranges, c0 + (int64_t)(range + 1) * total / n_ranges};
+    // bound(tg) = the first tile of cost >= tg (cost is increasing): round 0 counts the samples t = i st below
+    // each target, round 1 the tiles of the interval that leaves
+    const int64_t st = (n_tiles + NTH - 1) / NTH;
+    int64_t base[2] = {0, 0};
 #pragma unroll
-      for (int rd = 0; rd < 2; ++rd) {
-        int64_t c[2];
+    for (int rd = 0; rd < 2; ++rd) {
+      int64_t c[2];
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          const int64_t t = rd == 0 ? (int64_t)tid * st : base[k] + tid;
-          const bool ok = rd == 0 ? t < n_tiles : (tid < st - 1 && t < n_tiles);
-          c[k] = ok ? cost(t) : INT64_MAX;
-        }
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          const int n = __popcll(ballot64(c[k] < tg[k]));
-          if (lane == 0) bcnt[rd][k][wave] = n;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          int n = 0;
-#pragma unroll
-          for (int w = 0; w < NW; ++w) n += bcnt[rd][k][w];
-          base[k] = rd == 0 ? (n > 0 ? (int64_t)(n - 1) * st + 1 : 0) : base[k] + n;
-        }
+      for (int k = 0; k < 2; ++k) {
+        const int64_t t = rd == 0 ? (int64_t)tid * st : base[k] + tid;
+        const bool ok = rd == 0 ? t < n_tiles : (tid < st - 1 && t < n_tiles);
+        c[k] = ok ? cost(t) : INT64_MAX;
       }
-      t0 = base[0] < n_tiles ? base[0] : n_tiles;
-      t1 = base[1] < n_tiles ? base[1] : n_tiles;
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int n = __popcll(ballot64(c[k] < tg[k]));
+        if (lane == 0) bcnt[rd][k][wave] = n;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        int n = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) n += bcnt[rd][k][w];
+        base[k] = rd == 0 ? (n > 0 ? (int64_t)(n - 1) * st + 1 : 0) : base[k] + n;
+      }
     }
+    t0 = base[0] < n_tiles ? base[0] : n_tiles;
+    t1 = base[1] < n_tiles ? base[1] : n_tiles;
   }
 
   floatx4 acc[NOW][2][2];
@@ -1178,12 +1096,12 @@ __global__ __launch_bounds__(64 * NW, 1) void wgrad_x6c_kernel(
 
   // zero rows (never overwritten) and the padding chunk of the rule words
   for (int i = tid; i < 3 * 32; i += NTH) {
-    xim[(i / 32) * kWXImg + kWCap * RS + (i % 32)] = 0;
-    dim[(i / 32) * kWDImg + kWTile * RS + (i % 32)] = 0;
+    xim[(i / 32) * kWXImg + kWCap * kWRS + (i % 32)] = 0;
+    dim[(i / 32) * kWDImg + kWTile * kWRS + (i % 32)] = 0;
   }
   if (tid < 16) ent[kWMaxCh * 16 + tid] = (uint32_t)kWCap | ((uint32_t)kWTile << 16);
-  if (DT && tid < 128) otab[tid >> 6][(tid >> 5) & 1][tid & 31] = 0;
-  if (DT) __syncthreads();
+  if (tid < 128) otab[tid >> 6][(tid >> 5) & 1][tid & 31] = 0;
+  __syncthreads();
 
   // ---- staging registers: rows of tile t + 1 (loaded at the start of t), then its values and rule words
   int32_t srow[XI];
@@ -1202,14 +1120,12 @@ __global__ __launch_bounds__(64 * NW, 1) void wgrad_x6c_kernel(
   auto issue_vals = [&](int64_t t) {  // values of tile t (rows in srow) and its rule words
 #pragma unroll
     for (int b = 0; b < XI; ++b) {
-      if ((ABL & 2) && t != t0) break;
       const int u = (tid + NTH * b) & 7;
       xv[b] = floatx4{0.f, 0.f, 0.f, 0.f};
       if (srow[b] >= 0) xv[b] = *reinterpret_cast<const floatx4*>(x + (int64_t)srow[b] * c_in + ci0 + 4 * u);
     }
 #pragma unroll
     for (int b = 0; b < DI; ++b) {
-      if ((ABL & 2) && t != t0) break;
       const int it = tid + NTH * b, u = it & 7;
       const int64_t row = t * kWTile + (it >> 3);
       dv[b] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -1223,58 +1139,41 @@ __global__ __launch_bounds__(64 * NW, 1) void wgrad_x6c_kernel(
       ev[b] = e < s_nch * 16 ? chunk_lr[c0 * 16 + e] : 0u;
     }
     co_v = tid < s_nch ? chunk_off[c0 + tid] : 255;
-    if (DT) {
-      co_p = tid < s_nch && tid > 0 ? chunk_off[c0 + tid - 1] : 255;
-      co_n = tid + 1 < s_nch ? chunk_off[c0 + tid + 1] : 255;
-    }
+    co_p = tid < s_nch && tid > 0 ? chunk_off[c0 + tid - 1] : 255;
+    co_n = tid + 1 < s_nch ? chunk_off[c0 + tid + 1] : 255;
   };
-  int buf = 0;  // DT: the offset-table buffer of the staged tile
-  bool first_store = true;
-  auto store = [&]() {  // the staged tile into LDS (DT: one barrier; DT 0: two, the offset table through LDS)
-    const bool images = !(ABL & 1) || first_store;
-    first_store = false;
+  int buf = 0;  // the offset-table buffer of the staged tile
+  auto store = [&]() {  // the staged tile into LDS (one barrier)
 #pragma unroll
     for (int b = 0; b < XI; ++b) {
-      if (images && srow[b] >= 0) {
+      if (srow[b] >= 0) {
         const int it = tid + NTH * b;
         uint2 pc[3];
         split4(xv[b], pc);
 #pragma unroll
         for (int pp = 0; pp < 3; ++pp)
-          *reinterpret_cast<uint2*>(xim + pp * kWXImg + wimg_off_rs<RS>(it >> 3, it & 7)) = pc[pp];
+          *reinterpret_cast<uint2*>(xim + pp * kWXImg + wimg_off(it >> 3, it & 7)) = pc[pp];
       }
     }
 #pragma unroll
     for (int b = 0; b < DI; ++b) {
-      if (!images) break;
       const int it = tid + NTH * b;
       uint2 pc[3];
       split4(dv[b], pc);
 #pragma unroll
       for (int pp = 0; pp < 3; ++pp)
-        *reinterpret_cast<uint2*>(dim + pp * kWDImg + wimg_off_rs<RS>(it >> 3, it & 7)) = pc[pp];
+        *reinterpret_cast<uint2*>(dim + pp * kWDImg + wimg_off(it >> 3, it & 7)) = pc[pp];
     }
 #pragma unroll
     for (int b = 0; b < EI; ++b) {
       const int e = tid + NTH * b;
       if (e < s_nch * 16) ent[e] = ev[b];
     }
-    if constexpr (DT) {  // this tile's table into buffer buf, the other buffer (read by the last tile) zeroed
-      if (tid < 64) otab[buf ^ 1][tid >> 5][tid & 31] = 0;
-      if (tid < s_nch) {
-        if (co_p != co_v) otab[buf][0][co_v] = tid;
-        if (co_n != co_v) otab[buf][1][co_v] = tid + 1;
-      }
-      __syncthreads();
-      return;
-    }
-    if (tid < s_nch) offs[tid] = (uint8_t)co_v;
-    if (tid < 64) otab[0][tid >> 5][tid & 31] = 0;
-    __syncthreads();
+    // this tile's table into buffer buf, the other buffer (read by the last tile) zeroed
+    if (tid < 64) otab[buf ^ 1][tid >> 5][tid & 31] = 0;
     if (tid < s_nch) {
-      const int o = offs[tid];
-      if (tid == 0 || offs[tid - 1] != o) otab[0][0][o] = tid;
-      if (tid == s_nch - 1 || offs[tid + 1] != o) otab[0][1][o] = tid + 1;
+      if (co_p != co_v) otab[buf][0][co_v] = tid;
+      if (co_n != co_v) otab[buf][1][co_v] = tid + 1;
     }
     __syncthreads();
   };
@@ -1299,21 +1198,15 @@ __global__ __launch_bounds__(64 * NW, 1) void wgrad_x6c_kernel(
       dr[h] = (int)(w >> 16);
     }
   };
-  auto rows_of = [&](int cA, bool hasB, int (&xr)[2], int (&dr)[2]) {
-    uint32_t wd[2];
-    words_of(cA, wd);
-    rows_from(wd, hasB, xr, dr);
-  };
   auto frag = [&](const uint16_t* img, const int (&rr)[2], int v) {
-    const uint2 lo = tr_read(img + wimg_off_rs<RS>(rr[0], v));
-    const uint2 hi = tr_read(img + wimg_off_rs<RS>(rr[1], v));
+    const uint2 lo = tr_read(img + wimg_off(rr[0], v));
+    const uint2 hi = tr_read(img + wimg_off(rr[1], v));
     return u32x4{lo.x, lo.y, hi.x, hi.y};
   };
-  uint32_t wcur[2] = {0u, 0u}, wnxt[2] = {0u, 0u};  // PW: this and the next k-step's rule words
-  auto kstep = [&](int cA, bool hasB, floatx4 (&ac)[2][2]) {
+  uint32_t wcur[2] = {0u, 0u}, wnxt[2] = {0u, 0u};  // this and the next k-step's rule words
+  auto kstep = [&](bool hasB, floatx4 (&ac)[2][2]) {
     int xr[2], dr[2];
-    if constexpr (PW) rows_from(wcur, hasB, xr, dr);
-    else rows_of(cA, hasB, xr, dr);
+    rows_from(wcur, hasB, xr, dr);
     u32x4 fb[2][3], fa[3];
 #pragma unroll
     for (int sb = 0; sb < 2; ++sb)
@@ -1325,22 +1218,13 @@ __global__ __launch_bounds__(64 * NW, 1) void wgrad_x6c_kernel(
       for (int pp = 0; pp < 3; ++pp) fa[pp] = frag(xim + pp * kWXImg, xr, 4 * sa + p4);
 #pragma unroll
       for (int sb = 0; sb < 2; ++sb) {
-        if constexpr (AC == 1) {
-          floatx4& d = ac[sa][sb];
-          d = mfma_bf16(fa[2], fb[sb][0], d);
-          d = mfma_bf16(fa[1], fb[sb][1], d);
-          d = mfma_bf16(fa[0], fb[sb][2], d);
-          d = mfma_bf16(fa[1], fb[sb][0], d);
-          d = mfma_bf16(fa[0], fb[sb][1], d);
-          d = mfma_bf16(fa[0], fb[sb][0], d);
-          continue;
-        }
-        floatx4 c = mfma_bf16(fa[2], fb[sb][0], floatx4{0.f, 0.f, 0.f, 0.f});
-        c = mfma_bf16(fa[1], fb[sb][1], c);
-        c = mfma_bf16(fa[0], fb[sb][2], c);
-        c = mfma_bf16(fa[1], fb[sb][0], c);
-        c = mfma_bf16(fa[0], fb[sb][1], c);
-        ac[sa][sb] += mfma_bf16(fa[0], fb[sb][0], c);
+        floatx4& d = ac[sa][sb];
+        d = mfma_bf16(fa[2], fb[sb][0], d);
+        d = mfma_bf16(fa[1], fb[sb][1], d);
+        d = mfma_bf16(fa[0], fb[sb][2], d);
+        d = mfma_bf16(fa[1], fb[sb][0], d);
+        d = mfma_bf16(fa[0], fb[sb][1], d);
+        d = mfma_bf16(fa[0], fb[sb][0], d);
       }
     }
   };
@@ -1369,21 +1253,19 @@ __global__ __launch_bounds__(64 * NW, 1) void wgrad_x6c_kernel(
       for (int a = 0; a < NOW; ++a) {  // constant slot index: acc[a] stays in registers
         for (int c = first[a]; c < endc[a]; c += 2, ++s) {
           if (s == s_vals && more) issue_vals(t + 1);
-          if constexpr (PW) {
-            if (c == first[a]) {
-              words_of(c, wcur);
-            } else {
-              wcur[0] = wnxt[0];
-              wcur[1] = wnxt[1];
-            }
-            if (c + 2 < endc[a]) words_of(c + 2, wnxt);
+          if (c == first[a]) {
+            words_of(c, wcur);
+          } else {
+            wcur[0] = wnxt[0];
+            wcur[1] = wnxt[1];
           }
-          kstep(c, c + 1 < endc[a], acc[a]);
+          if (c + 2 < endc[a]) words_of(c + 2, wnxt);
+          kstep(c + 1 < endc[a], acc[a]);
         }
       }
       if (n_st == 0 && more) issue_vals(t + 1);
       __syncthreads();  // reads of tile t done
-      if (DT) buf ^= 1;
+      buf ^= 1;
       if (more) store();
     }
   }
@@ -1483,12 +1365,10 @@ int msp_wgrad_chunk_ok(int64_t n_rows, int K, int c_in, int c_out) {
 // in isolation since the products accumulate straight into the tile sums (0.327 vs 0.347 ms,
 // profiles/r03/kbench_r03y_level0.log) but needs level 0's tile-local rulebook (see msp_conv_local_preferred):
 // 32 output channels stay on the pair lists.
-#ifndef MSP_CHUNK_NARROW  // 1: c_out = 32 too (level 0's 32 x 32 and, since round 5's 72-byte image rows, the
-#define MSP_CHUNK_NARROW 1  // decoder's 64 x 32: 0.490 vs 0.517 ms on the pair lists, profiles/r05/kbench_r05p_*)
-#endif
+// c_out = 32 too (level 0's 32 x 32 and, since round 5's 72-byte image rows, the decoder's 64 x 32: 0.490 vs 0.517 ms
+// on the pair lists, profiles/r05/kbench_r05p_*).
 int msp_wgrad_chunk_preferred(int64_t n_rows, int K, int c_in, int c_out) {
-  return msp_wgrad_chunk_ok(n_rows, K, c_in, c_out) && (c_out >= 64 || (MSP_CHUNK_NARROW && c_out == 32)) ? 1
-                                                                                                             : 0;
+  return msp_wgrad_chunk_ok(n_rows, K, c_in, c_out) && (c_out >= 64 || c_out == 32) ? 1 : 0;
 }
 
 int64_t msp_wgrad_chunk_ranges(int64_t n_rows, int c_in, int c_out) {
@@ -1600,15 +1480,13 @@ int msp_conv_wgrad_chunk(const float* x, int c_in, const float* dy, int c_out, i
   hipStream_t s = as_stream(stream);
   const int64_t n_tiles = ceil_div(n_rows, kWTile);
   const int64_t slices = (int64_t)(c_in / 32) * (c_out / 32);
-  // 72-byte image rows (RS = 36): 9-15 % faster than the swizzled 64-byte rows at every level
-  // (profiles/r05/kbexp_r05m_x6c_row_stride.log)
   // the offset deal table was fitted to the 27 offsets of a 3^3 submanifold filter; other maps deal round-robin
   if (K == 27)
-    wgrad_x6c_kernel<8, 1, 1, MSP_X6C_RS, 0, 1, 128, 1><<<(unsigned)(n_ranges * slices), 512, 0, s>>>(
+    wgrad_x6c_kernel<true><<<(unsigned)(n_ranges * slices), 512, 0, s>>>(
         x, c_in, dy, c_out, K, tile_start, chunk_off, chunk_lr, u_start, u_rows, n_rows, n_tiles, (int)n_ranges,
         slab);
   else
-    wgrad_x6c_kernel<8, 1, 1, MSP_X6C_RS, 0, 1, 128, 0><<<(unsigned)(n_ranges * slices), 512, 0, s>>>(
+    wgrad_x6c_kernel<false><<<(unsigned)(n_ranges * slices), 512, 0, s>>>(
         x, c_in, dy, c_out, K, tile_start, chunk_off, chunk_lr, u_start, u_rows, n_rows, n_tiles, (int)n_ranges,
         slab);
   const int64_t n4 = (int64_t)K * c_in * c_out / 4;
@@ -1672,12 +1550,9 @@ int msp_split_weight_images(const msp_weight_image* descs, int n, const int64_t*
 // 5's backward-data 192 -> 384: 0.063 vs 0.086 ms on the shared tiles, profiles/r03/kbench_r03_split.log).  Level
 // 0's 32 -> 64 backward-data is faster here in isolation (0.685 vs 0.711 ms, profiles/r03/kbench_r03y_level0.log),
 // but it needs level 0's tile-local rulebook, whose side-stream build cost more than that: 57.1 vs 56.7 ms/step
-// with MSP_LOCAL_MIN_CIN 32 and MSP_CHUNK_NARROW 1 (profiles/r03/ab_r03_level0_local.log).
-#ifndef MSP_LOCAL_MIN_CIN  // experiments build: -DMSP_LOCAL_MIN_CIN=32 takes level 0's 32 -> 64
-#define MSP_LOCAL_MIN_CIN 64
-#endif
+// with level 0's 32 -> 64 routed here (profiles/r03/ab_r03_level0_local.log).
 int msp_conv_local_preferred(int64_t n_rows, int c_in, int c_out) {
-  return (c_in % 16 == 0 && c_out % 16 == 0 && c_in >= MSP_LOCAL_MIN_CIN && c_out >= 64 &&
+  return (c_in % 16 == 0 && c_out % 16 == 0 && c_in >= 64 && c_out >= 64 &&
           (n_rows >= 4096 || (n_rows >= 1024 && c_out >= 2 * c_in))) ? 1 : 0;
 }
 
@@ -1721,8 +1596,8 @@ int msp_conv_local_bn(const float* x, int c_in, const float* wt, int K, int flip
   const unsigned grid = (unsigned)(n_tiles * n_y);
   const BnEpi be = bn_epi_of(epi, c_out, n_rows);
 #define X6S(N, E)                                                                                                \
-  conv_x6s_kernel<N, 0, 1, 1, E><<<grid, 512, 0, s>>>(x, c_in, img, K, flip & 1, c_out, lidx, u_start, u_rows, perm, \
-                                                     wave_off, n_pad, n_y, out, be)
+  conv_x6s_kernel<N, 0, E><<<grid, 512, 0, s>>>(x, c_in, img, K, flip & 1, c_out, lidx, u_start, u_rows, perm, \
+                                               wave_off, n_pad, n_y, out, be)
   if (NT == 2) {
     if (epi) X6S(2, true);
     else X6S(2, false);
@@ -1735,10 +1610,9 @@ int msp_conv_local_bn(const float* x, int c_in, const float* wt, int K, int flip
 }
 
 #ifdef MSP_EXPERIMENTS
-// Kernel-variant entry for scripts/kbench.py (built only into lib/libmi3dsparse_exp.so by
-// scripts/build_exp.sh; the product library has no such symbol): msp_conv_local with the conv_x6s
-// template form selected by `variant` = 1000 (WB - 1) + 100 AB + 10 AC + RR (RR = 1: offsets dealt round-robin,
-// wave_off ignored).
+// Kernel-variant entry for scripts/kbench.py (built only into lib/libmi3dsparse_exp.so by `make exp`; the product
+// library has no such symbol): msp_conv_local with the conv_x6s template form selected by `variant` = 100 AB + 10 +
+// RR (RR = 1: offsets dealt round-robin, wave_off ignored).
 int msp_exp_conv_local(int variant, const float* x, int c_in, const float* wt, int K, int flip, int c_out,
                        int tile_rows, const uint16_t* lidx, const int64_t* u_start, const int32_t* u_rows,
                        const int32_t* perm, const uint8_t* wave_off, int64_t n_rows, float* out, void* ws,
@@ -1756,78 +1630,17 @@ int msp_exp_conv_local(int variant, const float* x, int c_in, const float* wt, i
   const unsigned grid = (unsigned)(n_tiles * n_y);
   const int64_t n_pad = n_tiles * tile_rows;
   const uint8_t* wo = variant % 10 == 1 ? nullptr : wave_off;
-  const int wbv = variant / 1000 + 1;
-  variant %= 1000;
-#define EV(A, C, W)                                                                                            \
-  if (wbv == W && variant / 100 == A && (variant / 10) % 10 == C) {                                            \
-    conv_x6s_kernel<2, A, C, W><<<grid, 512, 0, s>>>(x, c_in, img, K, flip & 1, c_out, lidx, u_start, u_rows,  \
-                                                     perm, wo, n_pad, n_y, out, BnEpi{});                      \
+#define EV(V, A)                                                                                               \
+  if (variant == V) {                                                                                          \
+    conv_x6s_kernel<2, A><<<grid, 512, 0, s>>>(x, c_in, img, K, flip & 1, c_out, lidx, u_start, u_rows, perm,  \
+                                               wo, n_pad, n_y, out, BnEpi{});                                  \
     return check_launch("msp_exp_conv_local");                                                                 \
   }
-  EV(0, 0, 1) EV(0, 1, 1) EV(1, 0, 1) EV(1, 1, 1) EV(4, 0, 1) EV(5, 0, 1) EV(8, 1, 1) EV(0, 1, 2)
+  EV(10, 0) EV(11, 0) EV(110, 1) EV(810, 8)
 #undef EV
 
   set_error("msp_exp_conv_local: no variant %d", variant);
   return MSP_EINVAL;
-}
-
-// msp_conv_wgrad_chunk with the wgrad_x6c template form selected by `variant` = AC (0 or 1).
-int msp_exp_wgrad_chunk(int variant, const float* x, int c_in, const float* dy, int c_out, int K, int tile_rows,
-                        const int64_t* tile_start, const uint8_t* chunk_off, const uint32_t* chunk_lr,
-                        const int64_t* u_start, const int32_t* u_rows, int64_t n_rows, int64_t n_ranges,
-                        float* slab, float* dw, msp_stream_t stream) {
-  MSP_REQUIRE(msp_wgrad_chunk_ok(n_rows, K, c_in, c_out) && tile_rows == kWTile && n_ranges >= 1,
-              "msp_exp_wgrad_chunk: shape");
-  hipStream_t s = as_stream(stream);
-  const int64_t n_tiles = ceil_div(n_rows, kWTile);
-  const int64_t slices = (int64_t)(c_in / 32) * (c_out / 32);
-  const unsigned grid = (unsigned)(n_ranges * slices);
-  if (variant == 0)
-    wgrad_x6c_kernel<8, 0, 0><<<grid, 512, 0, s>>>(x, c_in, dy, c_out, K, tile_start, chunk_off, chunk_lr, u_start,
-                                                u_rows, n_rows, n_tiles, (int)n_ranges, slab);
-  else if (variant == 1)
-    wgrad_x6c_kernel<8, 1, 0><<<grid, 512, 0, s>>>(x, c_in, dy, c_out, K, tile_start, chunk_off, chunk_lr, u_start,
-                                                u_rows, n_rows, n_tiles, (int)n_ranges, slab);
-  else if (variant == 3)
-    wgrad_x6c_kernel<8, 1, 1><<<grid, 512, 0, s>>>(x, c_in, dy, c_out, K, tile_start, chunk_off, chunk_lr, u_start,
-                                                   u_rows, n_rows, n_tiles, (int)n_ranges, slab);
-  else if (variant == 43)  // the product form with 72-byte image rows (RS = 36)
-    wgrad_x6c_kernel<8, 1, 1, 36><<<grid, 512, 0, s>>>(x, c_in, dy, c_out, K, tile_start, chunk_off, chunk_lr,
-                                                       u_start, u_rows, n_rows, n_tiles, (int)n_ranges, slab);
-  else if (variant == 143)  // ablation: no image staging after the first tile
-    wgrad_x6c_kernel<8, 1, 1, 36, 1><<<grid, 512, 0, s>>>(x, c_in, dy, c_out, K, tile_start, chunk_off, chunk_lr,
-                                                          u_start, u_rows, n_rows, n_tiles, (int)n_ranges, slab);
-  else if (variant == 343)  // ablation: no image staging and no value loads after the first tile
-    wgrad_x6c_kernel<8, 1, 1, 36, 3><<<grid, 512, 0, s>>>(x, c_in, dy, c_out, K, tile_start, chunk_off, chunk_lr,
-                                                          u_start, u_rows, n_rows, n_tiles, (int)n_ranges, slab);
-  else if (variant == 2043)  // the round-6 product: direct offset table (DT)
-    wgrad_x6c_kernel<8, 1, 1, 36, 0, 1><<<grid, 512, 0, s>>>(x, c_in, dy, c_out, K, tile_start, chunk_off, chunk_lr,
-                                                             u_start, u_rows, n_rows, n_tiles, (int)n_ranges, slab);
-  else if (variant == 32043)  // + ranges of equal cost, 32 chunks per tile of staging
-    wgrad_x6c_kernel<8, 1, 1, 36, 0, 1, 32><<<grid, 512, 0, s>>>(x, c_in, dy, c_out, K, tile_start, chunk_off,
-                                                                 chunk_lr, u_start, u_rows, n_rows, n_tiles,
-                                                                 (int)n_ranges, slab);
-  else if (variant == 64043)  // + ranges of equal cost, 64 chunks per tile of staging
-    wgrad_x6c_kernel<8, 1, 1, 36, 0, 1, 64><<<grid, 512, 0, s>>>(x, c_in, dy, c_out, K, tile_start, chunk_off,
-                                                                 chunk_lr, u_start, u_rows, n_rows, n_tiles,
-                                                                 (int)n_ranges, slab);
-  else if (variant == 1128043)  // the round-6 product: + the offset deal table
-    wgrad_x6c_kernel<8, 1, 1, 36, 0, 1, 128, 1><<<grid, 512, 0, s>>>(x, c_in, dy, c_out, K, tile_start, chunk_off,
-                                                                     chunk_lr, u_start, u_rows, n_rows, n_tiles,
-                                                                     (int)n_ranges, slab);
-  else if (variant == 128043)  // + ranges of equal cost, 128 chunks per tile of staging
-    wgrad_x6c_kernel<8, 1, 1, 36, 0, 1, 128><<<grid, 512, 0, s>>>(x, c_in, dy, c_out, K, tile_start, chunk_off,
-                                                                  chunk_lr, u_start, u_rows, n_rows, n_tiles,
-                                                                  (int)n_ranges, slab);
-  else {
-    set_error("msp_exp_wgrad_chunk: no variant %d", variant);
-    return MSP_EINVAL;
-  }
-  const int64_t n4 = (int64_t)K * c_in * c_out / 4;
-  wgrad_ranges_reduce_kernel<<<(unsigned)ceil_div(n4, 16), 256, 0, s>>>(reinterpret_cast<const floatx4*>(slab),
-                                                                         (int)n_ranges, n4,
-                                                                         reinterpret_cast<floatx4*>(dw));
-  return check_launch("msp_exp_wgrad_chunk");
 }
 #endif
 

@@ -152,19 +152,12 @@ static int fill_bytes(void* p, uint8_t value, size_t bytes, hipStream_t s, const
 // Block hash of a level's sorted keys (msp_hash_build / msp_subm_map): one slot per occupied block of 32
 // consecutive Morton codes (2 x 4 x 4 sites), {key >> 5, first row << 32 | occupancy mask}.  The keys being
 // sorted, a block's rows are contiguous, so row(key) = first + popc(mask below key's code): one 16-byte load
-// answers every site of the block.  The slot is the block key's low bits (Morton-adjacent blocks share cache
-// lines, a wave's 64 rows look up a handful of lines) plus a mix of the bits above the table size (batch, far
-// regions), so scenes land apart.  Round 1-4 hashed every site with a mixing hash into a table of 2n random
+// answers every site of the block.  The slot is a mixing hash of the block key (the key's low bits as the slot, for
+// locality, lost to long linear-probe runs: DESIGN.md §3.9).  Round 1-4 hashed every site with a mixing hash into a table of 2n random
 // slots and wrote the map's mirror half by scatter after a memset of all K n entries.
 constexpr int kBlockBits = 5;
 constexpr unsigned kMapBlocks = 4096;  // grid cap of the counted submanifold map
-#ifndef MSP_BLOCK_SLOT_LOCAL  // experiments: 1 = the slot is the block key's low bits (+ a mix of the rest)
-#define MSP_BLOCK_SLOT_LOCAL 0
-#endif
-__device__ __forceinline__ uint64_t block_slot(uint64_t bk, uint64_t mask) {
-  if (MSP_BLOCK_SLOT_LOCAL) return (bk + hash_key(bk >> __popcll(mask))) & mask;
-  return hash_key(bk) & mask;
-}
+__device__ __forceinline__ uint64_t block_slot(uint64_t bk, uint64_t mask) { return hash_key(bk) & mask; }
 
 __global__ __launch_bounds__(kThreads) void hash_build_kernel(const uint64_t* __restrict__ keys, int64_t n,
                                                               uint64_t* __restrict__ table, uint64_t mask) {

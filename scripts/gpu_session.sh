@@ -9,8 +9,8 @@
 #   prof     rocprofv3 kernel trace + stats of the bench (scripts/gpu_profile.sh)
 #   traffic  PMC FETCH_SIZE / WRITE_SIZE of the conv family (scripts/pmc_traffic.sh)
 #   pmc      per-kernel PMC summary (scripts/gpu_pmc.sh)
-#   kbench   scripts/kbench.py on the product library (LEVELS / PASSES / FORMS / X6R_VARIANTS ... passed through)
-#   kbexp    scripts/kbench.py on the experiments build (lib/libmi3dsparse_exp.so, scripts/build_exp.sh)
+#   kbench   scripts/kbench.py on the product library (LEVELS / PASSES / FORMS / WFORMS ... passed through)
+#   kbexp    scripts/kbench.py on the experiments build (lib/libmi3dsparse_exp.so, `make exp`)
 #   ab       interleaved end-to-end A/B of the product and experiments builds (scripts/gpu_ab.sh)
 #   args     interleaved bench.py argument sets ARGS_0.. (scripts/gpu_args_ab.sh)
 #   n2gloo   the two-rank shared-device rehearsal of bench.py's N>1 path with per-rank host timing

@@ -83,31 +83,8 @@ def conv_forms(rules, V, cin, cout):
                     raise RuntimeError(lib.msp_last_error().decode())
                 return out
             return f
-        for v in [int(t) for t in os.environ.get("EXP_VARIANTS", "0,1").split(",") if t]:
+        for v in [int(t) for t in os.environ.get("EXP_VARIANTS", "10,11").split(",") if t]:
             forms[f"x6s_v{v}"] = exp(v)
-    if hasattr(lib, "msp_exp_conv_x6r") and cout <= 32 and cin <= 64:  # experiments build: per-wave tile variants
-        import ctypes
-        fx = lib.msp_exp_conv_x6r
-        P, I, I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-        fx.restype = I
-        fx.argtypes = [I, P, I, P, I, I, I, I, P, P, P, P, I64, P, P, ctypes.c_size_t, P]
-
-        def x6r(variant):
-            tr = 64 if variant % 10 == 1 else 128
-
-            def f(x, wt, flip):
-                tl = rules.tiles_for(tr)
-                out = torch.empty(V, cout, device=DEV)
-                wsb = 27 * cout * ((cin + 31) // 32) * 32 * 6 + 1024 + (V * cin * 6 if variant >= 100 else 0)
-                ws = torch.empty(max(wsb // 4, 1), device=DEV)
-                rc = fx(variant, ptr(x), cin, ptr(wt), 27, flip, cout, tr, ptr(tl["tile_start"]), ptr(tl["chunk_off"]),
-                        ptr(tl["chunk_src"]), ptr(tl["chunk_row"]), V, ptr(out), ptr(ws), wsb, _lib.stream())
-                if rc:
-                    raise RuntimeError(lib.msp_last_error().decode())
-                return out
-            return f
-        for v in [int(t) for t in os.environ.get("X6R_VARIANTS", "30,31,20,21").split(",") if t]:
-            forms[f"x6r_v{v}"] = x6r(v)
     if hasattr(ops, "conv_unit") and cout <= 64:
         forms["unit"] = lambda x, wt, flip: ops.conv_unit(x, wt, 27, flip, cout, rules, V)
     if FORMS:
@@ -261,47 +238,17 @@ def main():
                 fs = {"pairs": lambda: ops.conv_wgrad(x, dy, p, p.pair_in, p.pair_out, 27)}
                 if int(_lib.query("msp_wgrad_chunk_ok", _lib.I64(V), 27, cin, cout)) and rules.wgrad_index() is not None:
                     fs["chunk"] = lambda: ops.conv_wgrad_chunk(x, dy, rules, 27)
-                lib = _lib.load()
-                if "chunk" in fs and hasattr(lib, "msp_exp_wgrad_chunk"):  # MSP_EXPERIMENTS: wgrad_x6c variants
-                    import ctypes
-                    fn = lib.msp_exp_wgrad_chunk
-                    P, I, I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-                    fn.restype = I
-                    fn.argtypes = [I, P, I, P, I, I, I, P, P, P, P, P, I64, I64, P, P, P]
-
-                    def wexp(variant, x=x, dy=dy, cin=cin, cout=cout):
-                        def f():
-                            idx = rules.wgrad_index()
-                            tiles = idx["tiles"]
-                            ranges = int(_lib.query("msp_wgrad_chunk_ranges", _lib.I64(V), cin, cout))
-                            dw = torch.empty((27, cin, cout), device=DEV)
-                            slab = torch.empty((ranges, 27, cin, cout), device=DEV)
-                            rc = fn(variant, ptr(x), cin, ptr(dy), cout, 27, tiles["tile_rows"], ptr(tiles["tile_start"]),
-                                    ptr(tiles["chunk_off"]), ptr(idx["chunk_lr"]), ptr(idx["u_start"]), ptr(idx["u_rows"]),
-                                    V, ranges, ptr(slab), ptr(dw), _lib.stream())
-                            if rc:
-                                raise RuntimeError(lib.msp_last_error().decode())
-                            return dw
-                        return f
-                    for v in [int(t) for t in os.environ.get("WEXP_VARIANTS", "0,1").split(",") if t]:
-                        fs[f"x6c_v{v}"] = wexp(v)
                 if WFORMS:
                     fs = {k: v for k, v in fs.items() if k in WFORMS.split(",")}
                 if hasattr(ops, "conv_wgrad_unit"):
                     fs["unit"] = lambda: ops.conv_wgrad_unit(x, dy, rules, 27)
-                res, first_x6c = [], None
+                res = []
                 for name, f in fs.items():
                     try:
                         ms = timeit(f)
                         out = f()
                         err = (out.double() - ref).abs().max().item() / scale
-                        same = ""
-                        if name.startswith("x6c_v"):  # bit-identity against the first variant listed
-                            if first_x6c is None:
-                                first_x6c = out
-                            else:
-                                same = " =" if torch.equal(out, first_x6c) else " !="
-                        res.append(f"{name} {ms:6.3f}ms {flops / ms / 1e9:6.1f}TF {err:.0e}{same}")
+                        res.append(f"{name} {ms:6.3f}ms {flops / ms / 1e9:6.1f}TF {err:.0e}")
                     except Exception as e:
                         res.append(f"{name} n/a ({str(e)[:40]})")
                 print(f"  wgrad {cin:3d}x{cout:3d}  " + "  ".join(res), flush=True)

@@ -1,7 +1,7 @@
 """msp_conv_pairs micro-benchmark on the headline batch (8 synthetic scenes at scale 50, the m = 32 UNet's strided
 relations): per level L -> L+1, the deconvolution forward (coarse 32(L+2) channels -> fine 32(L+1)) and the strided
 convolution's backward-data (same shapes), which are the two users of the pair-list convolution.  Times the product
-library and, through each lib/libmi3dsparse_exp*.so (scripts/build_exp.sh, e.g. EXP_FLAGS=-DMSP_PAIRS_RUN=0), the same
+library and, through each lib/libmi3dsparse_exp*.so (scripts/build_exp.sh with EXP_FLAGS), the same
 call through it, and checks the two outputs are bit-identical.  HIP events, median of N.
 
 Usage: python scripts/kbench_pairs.py   env: N=20  SCENES=8  M=32"""

@@ -39,14 +39,6 @@ def main():
     b = make_batch(int(os.environ.get("SCENES", "8")), 50, seed=1)
     t = scn.InputLayer(3, 4096, mode=4)([torch.from_numpy(b["coords"]).to(DEV), torch.from_numpy(b["feats"]).to(DEV)])
     meta = t.metadata
-    variants = [int(v) for v in os.environ.get("VARIANTS", "").split(",") if v]
-    lib = _lib.load()
-    exp = getattr(lib, "msp_exp_conv_pairs_x6", None)
-    if exp is not None:
-        import ctypes
-        P, I, I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-        exp.restype = I
-        exp.argtypes = [I, P, I, P, I, I, P, P, P, P, I64, P, P, ctypes.c_size_t, P]
     tot = {}
     for L in LEVELS:
         fine_size = 4096 >> L
@@ -64,21 +56,16 @@ def main():
         wsb = int(_lib.query("msp_conv_pairs_x6_workspace_size", K, cin, cout))
         ws = torch.empty(wsb // 4 + 4, device=DEV)
 
-        def run(kind, variant=0):
+        def run(kind):
             out = torch.empty(n_fine, cout, device=DEV)
 
             def f():
                 if kind == "f32":
                     _lib.call("msp_conv_pairs", ptr(x), cin, ptr(wt), K, cout, ptr(p.pair_out), ptr(p.pair_in),
                               ptr(p.off_start), ptr(p.chunk_start), p.n_chunks, ptr(out), _lib.stream())
-                elif kind == "x6":
+                else:
                     _lib.call("msp_conv_pairs_x6", ptr(x), cin, ptr(wt), K, cout, ptr(p.pair_out), ptr(p.pair_in),
                               ptr(p.off_start), ptr(p.chunk_start), p.n_chunks, ptr(out), ptr(ws), wsb, _lib.stream())
-                else:
-                    rc = exp(variant, ptr(x), cin, ptr(wt), K, cout, ptr(p.pair_out), ptr(p.pair_in),
-                             ptr(p.off_start), ptr(p.chunk_start), p.n_chunks, ptr(out), ptr(ws), wsb,
-                             _lib.stream())
-                    assert rc == 0, lib.msp_last_error()
             return f, out
 
         # fp64 on a subset of output rows
@@ -89,13 +76,11 @@ def main():
             offs[os_[o]:os_[o + 1]] = o
         sel = torch.randperm(p.total, device=DEV)[:4096]
         ref = torch.einsum("nc,noc->no", x[pin[sel]].double(), wt[offs[sel]].double())
-        forms = [("f32", 0), ("x6", 0)] + [("exp", v) for v in variants]
         line = []
-        for kind, v in forms:
-            f, out = run(kind, v)
+        for name in ("f32", "x6"):
+            f, out = run(name)
             ms = timeit(f)
             err = (out[pout[sel]].double() - ref).abs().max().item() / ref.abs().max().item()
-            name = kind if kind != "exp" else f"exp{v}"
             tot[name] = tot.get(name, 0.0) + ms
             line.append(f"{name} {ms * 1e3:7.1f} us {nbytes / ms / 1e6:6.0f} GB/s {flops / ms / 1e9:6.1f} TF/s "
                         f"err {err:.1e}")
