@@ -29,7 +29,7 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import I64, call, ptr, query
+from ._lib import call, ptr, query
 
 CHUNK = 16      # MSP_CHUNK
 
@@ -156,7 +156,7 @@ def tile_rulebook(m, K, n, device, s, tile_rows=64):
     n_tiles = (n + tr - 1) // tr
     # tile_start[n_tiles + 1] = largest chunk count of one tile
     tile_start = torch.empty(n_tiles + 2, dtype=torch.int64, device=device)
-    ws = _ws((n_tiles + 1) * 8 + query("msp_scan_workspace_size", I64(n_tiles)), device)
+    ws = _ws((n_tiles + 1) * 8 + query("msp_scan_workspace_size", n_tiles), device)
     call("msp_tile_rulebook", ptr(m), K, n, tr, ptr(tile_start), None, None, None, 0, ptr(ws), ws.numel(), s)
     out = dict(tile_start=tile_start, tile_rows=tr)
 
@@ -184,7 +184,7 @@ def local_rulebook(nbr, K, n, device, s, tile_rows=LOCAL_TILE_ROWS, lists_only=F
     T = int(tile_rows)
     n_tiles = (n + T - 1) // T
     u_start = torch.empty(n_tiles + 2, dtype=torch.int64, device=device)
-    ws = _ws(query("msp_tile_local_workspace_size", I64(n), T), device)
+    ws = _ws(query("msp_tile_local_workspace_size", n, T), device)
     call("msp_tile_local", ptr(nbr), K, n, T, ptr(u_start), None, 0, None, None, None, ptr(ws), ws.numel(), s)
     out = dict(u_start=u_start, tile_rows=T, n_tiles=n_tiles)
 
@@ -229,7 +229,7 @@ class PairLists:
     def __init__(self, m, K, n, device, s, plan=None, key=None):
         nrb = max(1, (n + 2047) // 2048)
         mm = K * nrb
-        ws = _ws((2 * mm + 1) * 8 + query("msp_scan_workspace_size", I64(mm)), device)
+        ws = _ws((2 * mm + 1) * 8 + query("msp_scan_workspace_size", mm), device)
         self.off_start = torch.empty(K + 1, dtype=torch.int64, device=device)
         call("msp_pair_lists", ptr(m), K, n, None, None, 0, ptr(self.off_start), ptr(ws), ws.numel(), s)
         # the filling call reuses the count's workspace (kept: a fill captured into a graph reads it at replay)
@@ -307,7 +307,7 @@ class SubmRules:
         # the rulebook size counted as the map is written (round 5; the pair lists' count pass over the map ran
         # for every level, though most never fill the lists)
         self._nr = torch.empty(1, dtype=torch.int64, device=dev)
-        ws = _ws(query("msp_subm_map_workspace_size", I64(V), filter_size), dev)
+        ws = _ws(query("msp_subm_map_workspace_size", V, filter_size), dev)
         call("msp_subm_map_counted", ptr(level.keys), V, level.log2, level.size, filter_size, ptr(table), cap,
              ptr(self.nbr), ptr(self._nr), ptr(ws), ws.numel(), s)
         self._tiles = {}
@@ -351,7 +351,7 @@ class SubmRules:
                 dev, s = self.nbr.device, _lib.stream(self.nbr.device)
                 perm = torch.empty(V, dtype=torch.int32, device=dev)
                 nbr_p = torch.empty((K, V), dtype=torch.int32, device=dev)
-                wsb = int(_lib.query("msp_dense_order_workspace_size", _lib.I64(V), K, DENSE_LOG2_WINDOW))
+                wsb = int(_lib.query("msp_dense_order_workspace_size", V, K, DENSE_LOG2_WINDOW))
                 ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
                 call("msp_dense_order", ptr(self.nbr), K, V, DENSE_LOG2_WINDOW, ptr(perm), ptr(nbr_p), ptr(ws), wsb,
                      s)
@@ -432,7 +432,7 @@ class SubmRules:
             n_far = torch.zeros(1, dtype=torch.int64, device=dev) if over else None
             if self._n:
                 call("msp_wgrad_chunk_index", ptr(tiles["tile_start"]), ptr(tiles["chunk_src"]),
-                     ptr(tiles["chunk_row"]), I64(self._n), ptr(loc["u_start"]), ptr(loc["u_rows"]), ptr(lr),
+                     ptr(tiles["chunk_row"]), self._n, ptr(loc["u_start"]), ptr(loc["u_rows"]), ptr(lr),
                      ptr(n_far), s)
             idx = self._wchunk = dict(tiles=tiles, chunk_lr=lr, u_start=loc["u_start"], u_rows=loc["u_rows"],
                                       n_far=0)
@@ -443,9 +443,9 @@ class SubmRules:
                     if nf:
                         key = torch.empty(nf, dtype=torch.int64, device=dev)
                         tile = torch.empty(nf, dtype=torch.int32, device=dev)
-                        ws = _ws(query("msp_wgrad_far_workspace_size", I64(nf)), dev)
+                        ws = _ws(query("msp_wgrad_far_workspace_size", nf), dev)
                         call("msp_wgrad_far_list", ptr(tiles["tile_start"]), ptr(tiles["chunk_off"]), ptr(lr),
-                             I64(self._n), I64(nf), ptr(key), ptr(tile), ptr(ws), ws.numel(), _lib.stream(dev))
+                             self._n, nf, ptr(key), ptr(tile), ptr(ws), ws.numel(), _lib.stream(dev))
                         idx.update(far_key=key, far_tile=tile, far_ws=ws)
                 _later(n_far, far)
         return self._wchunk
@@ -457,7 +457,7 @@ class SubmRules:
         dev, s, n = self._map.device, _lib.stream(self._map.device), self._n
         n_tiles = (n + 127) // 128
         tile_start = torch.empty(n_tiles + 2, dtype=torch.int64, device=dev)
-        ws = _ws(query("msp_tile_local_workspace_size", I64(n), 128), dev)
+        ws = _ws(query("msp_tile_local_workspace_size", n, 128), dev)
         call("msp_local_chunk_index", ptr(loc["lidx"]), ptr(loc["perm"]), self.K, n, ptr(tile_start), None, None,
              0, ptr(ws), ws.numel(), s)
         tiles = dict(tile_start=tile_start, tile_rows=128)
@@ -536,7 +536,7 @@ class Level:
 
     def hash(self):
         if self._hash is None:
-            cap = int(query("msp_hash_capacity", I64(self.n)))
+            cap = int(query("msp_hash_capacity", self.n))
             table = torch.empty((2 * cap,), dtype=torch.int64, device=self.device)  # {key, value} slots
             call("msp_hash_build", ptr(self.keys), self.n, ptr(table), cap, _lib.stream(self.device))  # (empties it)
             self._hash = (table, cap)
@@ -602,7 +602,7 @@ class Metadata:
         skeys = torch.empty_like(keys)
         perm = torch.empty_like(vals)
         if n:
-            wsb = int(query("msp_sort_workspace_size", I64(n), end_bit))
+            wsb = int(query("msp_sort_workspace_size", n, end_bit))
             ws = _ws(wsb, dev)
             call("msp_sort_pairs", ptr(keys), ptr(skeys), ptr(vals), ptr(perm), n, end_bit, ptr(ws), ws.numel(), s)
         seg_of = torch.empty_like(vals)

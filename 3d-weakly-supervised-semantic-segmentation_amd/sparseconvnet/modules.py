@@ -188,8 +188,8 @@ class Deconvolution(_ConvBase):
 
 
 class NetworkInNetwork(nn.Module):
-    """Per-site dense linear map: GEMMs on hipBLASLt via torch, weight gradient
-    on msp_conv_wgrad (ops.NetworkInNetworkFunction)."""
+    """Per-site dense linear map: forward and backward-data on msp_nin_gemm, weight
+    gradient on msp_conv_wgrad (ops.NetworkInNetworkFunction)."""
 
     def __init__(self, nIn, nOut, bias=False):
         super().__init__()

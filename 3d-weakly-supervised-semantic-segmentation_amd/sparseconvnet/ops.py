@@ -5,6 +5,42 @@ rulebooks); every forward and backward pass is one or more C-ABI calls on the
 current HIP stream.  Channel counts that are not multiples of 16 (the 3-channel
 colour input of the first SubmanifoldConvolution, models/SparseConvNet.py:62)
 are zero-padded to the MFMA chunk width here and sliced back.
+
+The A/B switches, each with its default and the measurement that set it.  They are module globals read at call
+time: tests and bench.py set them on this module.
+
+FUSE_BN_STATS (MI3DSPARSE_BN_EPILOGUE=1; off)
+    The BN -> SubM -> BN -> SubM chains of the residual blocks (models/SparseConvNet.py:63-69): the convolution
+    that feeds a training-mode BatchNorm leaves that BN's forward sums in its epilogue, and the backward-data of
+    the convolution a BatchNorm feeds leaves that BN's backward sums (msp_bn_epilogue), so the BN skips its own
+    statistics pass over the rows.  The BN family drops from 9.0 to 7.5 ms/step but the
+    convolutions' epilogues cost more than that: 50.08-50.20 vs 49.80-49.89 ms/step, interleaved on one box
+    (profiles/r06/ab_r06g_bnepi_on_off.txt).
+PAIRS_X6 (MI3DSPARSE_PAIRS_X6=0 turns it off; on), PAIRS_FORM its name in the recorded kinds
+    One contribution per output row (deconvolution forward, strided backward-data) on the split-bf16 MFMAs of
+    msp_conv_pairs_x6 instead of the exact fp32 16x16x4 MFMA chains of msp_conv_pairs
+    (profiles/r06/ab_r06px_pairs_x6.log).
+STRIDED_WGRAD_CHUNK (MI3DSPARSE_STRIDED_WGRAD_CHUNK=1; off)
+    Strided-convolution and deconvolution weight gradients on the chunk form over the child map: tiles of 128
+    coarse rows, their children's distinct fine rows staged once per tile; for the deconvolution the roles are
+    swapped and it gives dW^T per offset.  Slower than the per-offset pair lists on the headline step: the kernels
+    2.18 / 2.30 vs 1.94 / 2.01 ms per 5 steps (a 128-coarse-row tile names ~2.4 x 128 fine rows, often past the 448
+    staged, and 8 offsets leave the k-steps short), and the child maps' tile rulebooks, distinct-row lists and
+    far-rule lists add ~9 ms of prefetch host time and side-stream work: 61.0 vs 50.0-50.1 ms/step
+    (profiles/r06/ab_r06k_strided_wgrad_chunk.txt).  Kept for its tests (the far-rule path on dense children).
+WGRAD_CONCURRENT (bench.py --concurrent-wgrad; False)
+    Every weight gradient on a side stream beside the backward-data.  It saved 0.3 ms of 66.9 per step (round 2,
+    eager), inside the box-to-box spread, and the co-running kernels stretch each other's event-timed durations
+    (the conv roofline reads low).
+WGRAD_SIDE_ROWS (bench.py --wgrad-side-rows; 0)
+    Levels below this many rows run their weight gradient beside the backward-data.  Although neither fills the
+    chip below ~10^4 rows, the graph-captured step measured 54.6-54.8 ms with it at 2^14 rows and 54.6 at 2^16,
+    against 54.2 without (profiles/r03/args_r03_wgrad_side.log).
+FUSE_JOIN_SPLIT (True)
+    The UNet decoder's JoinTable -> BatchNormalization: the BN's backward writes the join inputs' gradients itself
+    (BatchNormJoinFunction) instead of a [V][C] dx that JoinFunction's backward then splits (msp_split_cols: one
+    read and one write of V x C floats per join, 0.26 ms/step at C3; profiles/r06/ab_r06ae_join_split.txt).
+    False: JoinFunction's split.
 """
 from __future__ import annotations
 
@@ -18,7 +54,14 @@ from . import _lib
 from . import weight_images as _wimg
 from ._lib import call, ptr
 
-_EMPTY = {}
+FUSE_BN_STATS = os.environ.get("MI3DSPARSE_BN_EPILOGUE", "0") == "1"
+PAIRS_X6 = os.environ.get("MI3DSPARSE_PAIRS_X6", "1") == "1"
+PAIRS_FORM = "x6" if PAIRS_X6 else "f32"
+STRIDED_WGRAD_CHUNK = os.environ.get("MI3DSPARSE_STRIDED_WGRAD_CHUNK", "0") == "1"
+WGRAD_CONCURRENT = False
+WGRAD_SIDE_ROWS = 0
+FUSE_JOIN_SPLIT = True
+
 # diagnosis (bench.py per-kind breakdowns): recorded kinds carry the call's shape, "[c_in x c_out : rows]"
 _SHAPES = os.environ.get("MI3DSPARSE_KIND_SHAPES") == "1"
 
@@ -39,6 +82,25 @@ def _pad_cols(x, c):
     return x if x.size(1) == c else F.pad(x, (0, c - x.size(1)))
 
 
+def _unpad_cols(x, c):
+    return x if x.size(1) == c else x[:, :c]
+
+
+def _pad_weight(w):
+    """Weights [K][1][c_in][c_out] (or [K][c_in][c_out]) as contiguous [K][pad16(c_in)][pad16(c_out)]."""
+    K, cin, cout = w.size(0), w.size(-2), w.size(-1)
+    w = w.reshape(K, cin, cout)
+    if cin % 16 == 0 and cout % 16 == 0:
+        return w.contiguous()
+    return F.pad(w, (0, _pad16(cout) - cout, 0, _pad16(cin) - cin))
+
+
+def _padded(x, weight):
+    """The pad prelude of a convolution forward: (x and weight zero-padded to the MFMA chunk width, c_in, c_out)."""
+    wp = _pad_weight(weight)
+    return _pad_cols(x.contiguous(), wp.size(1)), wp, weight.size(-2), weight.size(-1)
+
+
 def _check_feats(x):
     if not x.is_cuda:
         raise RuntimeError("sparseconvnet (mi3dsparse): features must be on a HIP device; there is no CPU path")
@@ -46,11 +108,13 @@ def _check_feats(x):
         raise TypeError(f"sparseconvnet (mi3dsparse): features must be float32, got {x.dtype}")
 
 
-def _pad_weight(w, cin_p, cout_p):
-    K, cin, cout = w.shape
-    if cin == cin_p and cout == cout_p:
-        return w.contiguous()
-    return F.pad(w, (0, cout_p - cout, 0, cin_p - cin))
+def _rows(n, c, device, fill, guard=None):
+    """[n][c] float32 rows that fill(out) writes: allocated with at least one row (a valid pointer for an empty
+    level) and sliced back; fill is skipped for n == 0 (or, given a guard, when it is false)."""
+    out = torch.empty((max(n, 1), c), dtype=torch.float32, device=device)
+    if (n if guard is None else guard):
+        fill(out)
+    return out[:n]
 
 
 def _workspace(entry, wt, n_rows, K, c_in, c_out, flip, wsb, device):
@@ -81,11 +145,11 @@ def conv_form(rules, n_rows, c_in, c_out, K):
     the tile height of msp_conv_tile -- the library's preference queries."""
     nbr = getattr(rules, "nbr", None)  # submanifold rules carry the neighbour map
     if nbr is not None and n_rows and K <= 27 and \
-            int(_lib.query("msp_conv_local_preferred", _lib.I64(n_rows), c_in, c_out)):
+            int(_lib.query("msp_conv_local_preferred", n_rows, c_in, c_out)):
         return "local"
-    if nbr is not None and n_rows and int(_lib.query("msp_conv_nbr_preferred", _lib.I64(n_rows), c_in, c_out)):
+    if nbr is not None and n_rows and int(_lib.query("msp_conv_nbr_preferred", n_rows, c_in, c_out)):
         return "nbr"
-    return int(_lib.query("msp_conv_tile_rows", _lib.I64(n_rows), c_in, c_out))
+    return int(_lib.query("msp_conv_tile_rows", n_rows, c_in, c_out))
 
 
 def prepare(rules, purpose, c_in, c_out):
@@ -103,7 +167,7 @@ def prepare(rules, purpose, c_in, c_out):
         else:
             rules.tiles_for(f)
     elif purpose == "wgrad":
-        if int(_lib.query("msp_wgrad_chunk_preferred", _lib.I64(n), K, c_in, c_out)):
+        if int(_lib.query("msp_wgrad_chunk_preferred", n, K, c_in, c_out)):
             if rules.wgrad_index() is not None:
                 return
         rules.pairs.fill()
@@ -112,23 +176,14 @@ def prepare(rules, purpose, c_in, c_out):
 
 
 # ------------------------------------------------------------------ BatchNorm statistics in convolution epilogues
-# The BN -> SubM -> BN -> SubM chains of the residual blocks (models/SparseConvNet.py:63-69): the submanifold
-# convolution that feeds a training-mode BatchNorm leaves that BN's forward sums in its epilogue, and the
-# backward-data of the convolution a BatchNorm feeds leaves that BN's backward sums (msp_bn_epilogue), so the BN
-# skips its own statistics pass over the rows.  Off by default (MI3DSPARSE_BN_EPILOGUE=1 turns it
-# on): the BN family drops from 9.0 to 7.5 ms/step but the convolutions' epilogues cost more than that -- 50.08-50.20
-# vs 49.80-49.89 ms/step, interleaved on one box (profiles/r06/ab_r06g_bnepi_on_off.txt).
-FUSE_BN_STATS = os.environ.get("MI3DSPARSE_BN_EPILOGUE", "0") == "1"
-
-
 class BnParts:
     """Channel-major BatchNorm partial sums [2][C][P] (+ the [2][C] tail msp_bn_bwd_apply_cm writes) that a
-    convolution epilogue fills, one slot per 128-row tile; `written` once a call filled them."""
+    convolution epilogue fills (FUSE_BN_STATS), one slot per 128-row tile; `written` once a call filled them."""
     __slots__ = ("buf", "P", "C", "written")
 
     def __init__(self, C, n_rows, device):
         self.C = int(C)
-        self.P = int(_lib.query("msp_conv_bn_parts", _lib.I64(n_rows)))
+        self.P = int(_lib.query("msp_conv_bn_parts", n_rows))
         self.buf = torch.empty(max(2 * self.C * (self.P + 1), 1), dtype=torch.float64, device=device)
         self.written = False
 
@@ -155,7 +210,7 @@ def bn_epi_ok(rules, n_rows, c_in, c_out, K):
         return True
     if f == "nbr":
         return False
-    return int(_lib.query("msp_conv_tile_form", _lib.I64(n_rows), c_in, c_out, f)) == 1
+    return int(_lib.query("msp_conv_tile_form", n_rows, c_in, c_out, f)) == 1
 
 
 def _epi_arg(epi):
@@ -164,6 +219,41 @@ def _epi_arg(epi):
     e = _lib.BnEpilogue(parts.buf.data_ptr(), xb.data_ptr() if xb is not None else None,
                         stats.data_ptr() if stats is not None else None, float(leak))
     return ctypes.byref(e)  # keeps e alive with the pointer
+
+
+def _fwd_epi(parts, rules, n_rows, wp, c_out):
+    """The epilogue that leaves the forward sums of the convolution's unpadded output in `parts`, for the
+    BatchNorm it feeds, when the form for these sizes has one (else None)."""
+    K, cin_p, cout_p = wp.shape
+    if parts is not None and cout_p == c_out and parts.C == c_out and bn_epi_ok(rules, n_rows, cin_p, cout_p, K):
+        return (parts, None, None, 0.0)
+    return None
+
+
+def _conv_tile_linked(g, wp, flip, rules, n_rows, link, kind, flops):
+    """The backward-data conv_tile of a convolution whose input a BatchNorm (link) produced: that BN gets its
+    backward sums from this call's epilogue when the form has one (link.bwd)."""
+    K, cin_p, cout_p = wp.shape
+    epi = None
+    if link is not None and link.x is not None and bn_epi_ok(rules, n_rows, cout_p, cin_p, K):
+        epi = (BnParts(cin_p, n_rows, g.device), link.x, link.stats, link.leak)
+    dxp = conv_tile(g, wp, K, flip, cin_p, rules, n_rows, kind, flops, epi=epi)
+    if epi is not None:
+        link.bwd = (dxp, epi[0])
+    return dxp
+
+
+def _conv_call(entry, args, epi, s, kind, flops, nbytes, n_out):
+    """The recorded convolution call entry(*args, s); with a BatchNorm epilogue `epi`, entry + "_bn", which takes
+    the msp_bn_epilogue before the stream and, in a backward-data (epi[1]: the BN input rows), also reads those
+    n_out values."""
+    if epi is None:
+        _record(kind, flops, lambda: call(entry, *args, s), nbytes)
+    else:
+        ea = _epi_arg(epi)
+        _record(kind, flops, lambda: call(entry + "_bn", *args, ea, s),
+                nbytes + (4 * n_out if epi[1] is not None else 0))
+        epi[0].written = True
 
 
 def conv_tile(x, wt, K, flip, c_out, rules, n_rows, kind="conv_tile", flops=0, epi=None):
@@ -176,111 +266,69 @@ def conv_tile(x, wt, K, flip, c_out, rules, n_rows, kind="conv_tile", flops=0, e
     if f == "local":
         return conv_local(x, wt, K, flip, c_out, rules, n_rows, kind, flops, epi)
     if epi is not None and (f == "nbr" or not n_rows or
-                            int(_lib.query("msp_conv_tile_form", _lib.I64(n_rows), c_in, c_out, f)) != 1):
+                            int(_lib.query("msp_conv_tile_form", n_rows, c_in, c_out, f)) != 1):
         raise RuntimeError("conv_tile: the BatchNorm epilogue needs the tile-local or per-wave form (bn_epi_ok)")
     if f == "nbr":
         perm, nbr_p = rules.dense_order()
         return conv_nbr(x, wt, K, flip, c_out, nbr_p, n_rows, kind, flops, perm)
     tr = f
     tiles = rules.tiles_for(tr)
-    out = torch.empty((max(n_rows, 1), c_out), dtype=torch.float32, device=x.device)
-    if n_rows:
+
+    def fill(out):
         # the contraction msp_conv_tile runs on 128-row tiles: bf16 MFMA over
         # exact three-piece operand splits (per-wave tiles for narrow outputs)
-        form = int(_lib.query("msp_conv_tile_form", _lib.I64(n_rows), c_in, c_out, tr))
-        kind = _shape(kind + {1: "/x6r", 2: "/x6d"}.get(form, "/f32"), c_in, c_out, n_rows)
-        wsb = int(_lib.query("msp_conv_tile_workspace_size", _lib.I64(n_rows), K, c_in, c_out, tr))
-        ws, wsb, flip = _workspace(0, wt, n_rows, K, c_in, c_out, int(flip), wsb, x.device)
+        form = int(_lib.query("msp_conv_tile_form", n_rows, c_in, c_out, tr))
+        wsb = int(_lib.query("msp_conv_tile_workspace_size", n_rows, K, c_in, c_out, tr))
+        ws, wsb, fl = _workspace(0, wt, n_rows, K, c_in, c_out, int(flip), wsb, x.device)
         # compulsory bytes: input rows, output rows, weights, rulebook (chunk
         # offsets, 16 x (int32 src + uint16 row) per chunk, tile starts)
         nbytes = 4 * (x.size(0) * c_in + n_rows * c_out + K * c_in * c_out) + \
             tiles["n_chunks"] * (1 + 16 * 6) + 8 * (tiles["tile_start"].numel())
-        if epi is None:
-            _record(kind, flops, lambda: call(
-                "msp_conv_tile", ptr(x), c_in, ptr(wt), K, int(flip), c_out, tr, ptr(tiles["tile_start"]),
-                ptr(tiles["chunk_off"]), ptr(tiles["chunk_src"]), ptr(tiles["chunk_row"]), n_rows, ptr(out),
-                ptr(ws), wsb, _stream(x)), nbytes)
-        else:  # + the epilogue's read of the BN input rows (backward)
-            ea = _epi_arg(epi)
-            _record(kind, flops, lambda: call(
-                "msp_conv_tile_bn", ptr(x), c_in, ptr(wt), K, int(flip), c_out, tr, ptr(tiles["tile_start"]),
-                ptr(tiles["chunk_off"]), ptr(tiles["chunk_src"]), ptr(tiles["chunk_row"]), n_rows, ptr(out),
-                ptr(ws), wsb, ea, _stream(x)), nbytes + (4 * n_rows * c_out if epi[1] is not None else 0))
-            epi[0].written = True
-    return out[:n_rows]
+        _conv_call("msp_conv_tile", (
+            ptr(x), c_in, ptr(wt), K, fl, c_out, tr, ptr(tiles["tile_start"]), ptr(tiles["chunk_off"]),
+            ptr(tiles["chunk_src"]), ptr(tiles["chunk_row"]), n_rows, ptr(out), ptr(ws), wsb), epi, _stream(x),
+            _shape(kind + {1: "/x6r", 2: "/x6d"}.get(form, "/f32"), c_in, c_out, n_rows), flops, nbytes,
+            n_rows * c_out)
+    return _rows(n_rows, c_out, x.device, fill)
 
 
 def conv_local(x, wt, K, flip, c_out, rules, n_rows, kind="conv_local", flops=0, epi=None):
     """Submanifold convolution over the tile-local rulebook (SubmRules.local): each 128-row tile's distinct
-    input rows staged in LDS and split once (msp_conv_local); epi: the BatchNorm epilogue (msp_conv_local_bn)."""
+    input rows staged in LDS and split once (msp_conv_local); epi: the BatchNorm epilogue (msp_conv_local_bn).
+    Without epi the library is called for an empty level too; with it, it is not (epi[0].written stays False)."""
     c_in = x.size(1)
     loc = rules.local()
-    out = torch.empty((max(n_rows, 1), c_out), dtype=torch.float32, device=x.device)
     wsb = int(_lib.query("msp_conv_local_workspace_size", K, c_in, c_out))
     ws, wsb, flip = _workspace(1, wt, n_rows, K, c_in, c_out, int(flip), wsb, x.device)
     # compulsory bytes: input rows, output rows, weights, the tile-local rulebook
     nbytes = 4 * (x.size(0) * c_in + n_rows * c_out + K * c_in * c_out) + \
         4 * loc["total"] + 2 * K * loc["n_tiles"] * loc["tile_rows"] + 4 * loc["n_tiles"] * loc["tile_rows"]
-    if epi is None:
-        _record(_shape(kind + "/x6s", c_in, c_out, n_rows), flops, lambda: call(
-            "msp_conv_local", ptr(x), c_in, ptr(wt), K, int(flip), c_out, loc["tile_rows"], ptr(loc["lidx"]),
-            ptr(loc["u_start"]), ptr(loc["u_rows"]), ptr(loc["perm"]), ptr(loc.get("wave_off")), n_rows, ptr(out),
-            ptr(ws), wsb, _stream(x)),
-            nbytes)
-    elif n_rows:  # + the epilogue's read of the BN input rows (backward)
-        ea = _epi_arg(epi)
-        _record(_shape(kind + "/x6s", c_in, c_out, n_rows), flops, lambda: call(
-            "msp_conv_local_bn", ptr(x), c_in, ptr(wt), K, int(flip), c_out, loc["tile_rows"], ptr(loc["lidx"]),
-            ptr(loc["u_start"]), ptr(loc["u_rows"]), ptr(loc["perm"]), ptr(loc.get("wave_off")), n_rows, ptr(out),
-            ptr(ws), wsb, ea, _stream(x)),
-            nbytes + (4 * n_rows * c_out if epi[1] is not None else 0))
-        epi[0].written = True
-    return out[:n_rows]
-
-
-# One contribution per output row (deconvolution forward, strided backward-data) on the split-bf16 MFMAs
-# (msp_conv_pairs_x6, round 6) instead of the exact fp32 16x16x4 MFMA chains of msp_conv_pairs.
-PAIRS_X6 = os.environ.get("MI3DSPARSE_PAIRS_X6", "1") == "1"
-PAIRS_FORM = "x6" if PAIRS_X6 else "f32"
+    return _rows(n_rows, c_out, x.device, lambda out: _conv_call("msp_conv_local", (
+        ptr(x), c_in, ptr(wt), K, flip, c_out, loc["tile_rows"], ptr(loc["lidx"]), ptr(loc["u_start"]),
+        ptr(loc["u_rows"]), ptr(loc["perm"]), ptr(loc.get("wave_off")), n_rows, ptr(out), ptr(ws), wsb), epi,
+        _stream(x), _shape(kind + "/x6s", c_in, c_out, n_rows), flops, nbytes, n_rows * c_out),
+        guard=epi is None or n_rows)
 
 
 def conv_pairs(x, wt, K, c_out, pairs, pin, pout, n_out, kind="pairs", flops=0):
-    """out[pout[p]] = wt[o]^T x[pin[p]] (wt [K][c_out][c_in]), one pair per output row."""
-    out = torch.empty((max(n_out, 1), c_out), dtype=torch.float32, device=x.device)
-    if pairs.n_chunks:
-        c_in = x.size(1)
+    """out[pout[p]] = wt[o]^T x[pin[p]] (wt [K][c_out][c_in]), one pair per output row (PAIRS_X6)."""
+    c_in = x.size(1)
+
+    def fill(out):
         # compulsory bytes: source rows, output rows, weights, the pair lists
         nbytes = 4 * (x.size(0) * c_in + n_out * c_out + K * c_in * c_out) + 8 * pairs.total
+        args = (ptr(x), c_in, ptr(wt), K, c_out, ptr(pin), ptr(pout), ptr(pairs.off_start), ptr(pairs.chunk_start),
+                pairs.n_chunks, ptr(out))
         if PAIRS_X6 and c_in % 16 == 0 and c_out % 16 == 0:
             wsb = int(_lib.query("msp_conv_pairs_x6_workspace_size", K, c_in, c_out))
             ws = torch.empty(max(wsb, 16) // 4 + 4, dtype=torch.float32, device=x.device)
-            _record(kind + "/x6", flops, lambda: call(
-                "msp_conv_pairs_x6", ptr(x), c_in, ptr(wt), K, c_out, ptr(pin), ptr(pout), ptr(pairs.off_start),
-                ptr(pairs.chunk_start), pairs.n_chunks, ptr(out), ptr(ws), wsb, _stream(x)), nbytes)
+            _record(kind + "/x6", flops, lambda: call("msp_conv_pairs_x6", *args, ptr(ws), wsb, _stream(x)), nbytes)
         else:
-            _record(kind + "/f32", flops, lambda: call(
-                "msp_conv_pairs", ptr(x), c_in, ptr(wt), K, c_out, ptr(pin), ptr(pout), ptr(pairs.off_start),
-                ptr(pairs.chunk_start), pairs.n_chunks, ptr(out), _stream(x)), nbytes)
-    return out[:n_out]
+            _record(kind + "/f32", flops, lambda: call("msp_conv_pairs", *args, _stream(x)), nbytes)
+    return _rows(n_out, c_out, x.device, fill, guard=pairs.n_chunks)
 
-
-# Strided-convolution and deconvolution weight gradients on the chunk form over the child map (round 6, opt-in:
-# MI3DSPARSE_STRIDED_WGRAD_CHUNK=1).  Measured slower than the per-offset pair lists on the headline step: the kernels
-# 2.18 / 2.30 vs 1.94 / 2.01 ms per 5 steps (a 128-coarse-row tile names ~2.4 x 128 fine rows, often past the 448
-# staged, and 8 offsets leave the k-steps short), and the child maps' tile rulebooks, distinct-row lists and far-rule
-# lists add ~9 ms of prefetch host time and side-stream work: 61.0 vs 50.0-50.1 ms/step
-# (profiles/r06/ab_r06k_strided_wgrad_chunk.txt).  Kept for its tests (the far-rule path on dense children).
-STRIDED_WGRAD_CHUNK = os.environ.get("MI3DSPARSE_STRIDED_WGRAD_CHUNK", "0") == "1"
 
 _WGRAD_SIDE = {}
-# True: every weight gradient on a side stream beside the backward-data (bench.py --concurrent-wgrad).
-# Off by default: it saved 0.3 ms of 66.9 per step (round 2, eager), inside the box-to-box spread, and the
-# co-running kernels stretch each other's event-timed durations (the conv roofline reads low).
-WGRAD_CONCURRENT = False
-# Levels below this many rows run their weight gradient beside the backward-data (bench.py --wgrad-side-rows).
-# Off: although neither fills the chip below ~10^4 rows, the graph-captured step measured 54.6-54.8 ms with it
-# at 2^14 rows and 54.6 at 2^16, against 54.2 without (profiles/r03/args_r03_wgrad_side.log).
-WGRAD_SIDE_ROWS = 0
 
 
 def _on_side(x, rows, fn):
@@ -318,7 +366,7 @@ def conv_wgrad_async(x, dy, pairs, pin, pout, K, flops=None, kind="wgrad"):
 def conv_wgrad(x, dy, pairs, pin, pout, K, kind="wgrad", flops=None):
     c_in, c_out = x.size(1), dy.size(1)
     dw = torch.empty((K, c_in, c_out), dtype=torch.float32, device=x.device)
-    n_pieces = int(_lib.query("msp_wgrad_pieces", _lib.I64(pairs.total), K, c_in, c_out))
+    n_pieces = int(_lib.query("msp_wgrad_pieces", pairs.total, K, c_in, c_out))
     slab = torch.empty((n_pieces, K, c_in, c_out), dtype=torch.float32, device=x.device)
     if flops is None:
         flops = 2.0 * pairs.total * c_in * c_out
@@ -339,7 +387,7 @@ def conv_wgrad_chunk(x, dy, rules, K, kind="wgrad", flops=None):
     c_in, c_out = x.size(1), dy.size(1)
     n = dy.size(0)
     tiles = idx["tiles"]
-    ranges = int(_lib.query("msp_wgrad_chunk_ranges", _lib.I64(n), c_in, c_out))
+    ranges = int(_lib.query("msp_wgrad_chunk_ranges", n, c_in, c_out))
     dw = torch.empty((K, c_in, c_out), dtype=torch.float32, device=x.device)
     slab = torch.empty((ranges, K, c_in, c_out), dtype=torch.float32, device=x.device)
     if flops is None:
@@ -358,20 +406,41 @@ def conv_wgrad_chunk(x, dy, rules, K, kind="wgrad", flops=None):
     return dw
 
 
+def _wgrad(rules, x, dy, K, dims, kind, flops, chunk=True, transposed=False):
+    """The weight gradient of a convolution Function: (dW [K][1][c_in][c_out] for the unpadded dims = (c_in,
+    c_out), join); call join() before the backward returns (_on_side).  With `chunk`, the chunk form when the
+    library prefers it for the rows of its tiled side (dy) and the rules have a tile index; else msp_conv_wgrad
+    over the pair lists (built by the prefetch when the batch's sizes select them: ops.prepare).  transposed (the
+    deconvolution, whose input is the rules' coarse side): the pair lists are read the other way round, and the
+    chunk form runs with x and dy swapped -- x's rows are the tiles' own -- and gives dW^T per offset."""
+    a, b = (dy, x) if transposed else (x, dy)
+    dwp = None
+    if chunk:
+        n, ca, cb = b.size(0), a.size(1), b.size(1)
+        rules.note_use("wgrad", ca, cb)
+        if int(_lib.query("msp_wgrad_chunk_preferred", n, K, ca, cb)) and rules.wgrad_index(wait=True) is not None:
+            dwp, join = _on_side(x, n, lambda: conv_wgrad_chunk(a, b, rules, K, kind, flops))
+            if transposed:
+                dwp = dwp.transpose(1, 2)
+    if dwp is None:
+        p = rules.pairs
+        pin, pout = (p.pair_out, p.pair_in) if transposed else (p.pair_in, p.pair_out)
+        dwp, join = conv_wgrad_async(x, dy, p, pin, pout, K, flops, kind)
+    return dwp[:, :dims[0], :dims[1]].reshape(K, 1, *dims), join
+
+
 def conv_nbr(x, wt, K, flip, c_out, nbr, n_rows, kind="conv_nbr", flops=0, perm=None):
     """Dense row-group form of the submanifold convolution straight from the
     neighbour map nbr[K][n_rows] (msp_conv_nbr: no tile rulebook); with perm,
     nbr is the map permuted by it (SubmRules.dense_order)."""
     c_in = x.size(1)
-    out = torch.empty((max(n_rows, 1), c_out), dtype=torch.float32, device=x.device)
     wsb = int(_lib.query("msp_conv_nbr_workspace_size", K, c_in, c_out))
     ws, wsb, flip = _workspace(2, wt, n_rows, K, c_in, c_out, int(flip), wsb, x.device)
     # compulsory bytes: input rows, output rows, weights, the neighbour map (+ row order)
     nbytes = 4 * (x.size(0) * c_in + n_rows * c_out + K * c_in * c_out + K * n_rows + (n_rows if perm is not None else 0))
-    _record(kind + "/x6g", flops, lambda: call(
-        "msp_conv_nbr", ptr(x), c_in, ptr(wt), K, int(flip), c_out, ptr(nbr), ptr(perm) if perm is not None else None,
-        n_rows, ptr(out), ptr(ws), wsb, _stream(x)), nbytes)
-    return out[:n_rows]
+    return _rows(n_rows, c_out, x.device, lambda out: _record(kind + "/x6g", flops, lambda: call(
+        "msp_conv_nbr", ptr(x), c_in, ptr(wt), K, flip, c_out, ptr(nbr), ptr(perm), n_rows, ptr(out), ptr(ws), wsb,
+        _stream(x)), nbytes), guard=True)  # (called for an empty level too)
 
 
 # ------------------------------------------------------------------ submanifold
@@ -387,32 +456,25 @@ class SubmanifoldConvFunction(torch.autograd.Function):
         K, _, cin, cout = weight.shape
         V = x.size(0)
         ctx.link = None
+        ctx.rules, ctx.dims = rules, (cin, cout)
         nbr = getattr(rules, "nbr", None)
-        if nbr is not None and int(_lib.query("msp_conv_narrow_in_ok", K, cin, cout)):
+        ctx.narrow = nbr is not None and bool(int(_lib.query("msp_conv_narrow_in_ok", K, cin, cout)))
+        if ctx.narrow:
             # the colour input layer (c_in <= 4): straight from the neighbour map, no channel padding
             xc, wc = x.contiguous(), weight.reshape(K, cin, cout).contiguous()
-            out = torch.empty((max(V, 1), cout), dtype=torch.float32, device=x.device)
-            if V:
-                nbytes = 4 * (V * cin + V * cout + K * cin * cout + K * V)
-                _record(_shape("subm_fwd/f32n", cin, cout, V), 2.0 * rules.n_rules * cin * cout, lambda: call(
-                    "msp_conv_narrow_in", ptr(xc), cin, ptr(wc), K, cout, ptr(nbr), V, ptr(out), _stream(x)), nbytes)
             ctx.save_for_backward(xc, wc)
-            ctx.rules, ctx.dims, ctx.narrow = rules, (cin, cout), True
-            return out[:V]
-        cin_p, cout_p = _pad16(cin), _pad16(cout)
-        xp = _pad_cols(x.contiguous(), cin_p)
-        wp = _pad_weight(weight.reshape(K, cin, cout), cin_p, cout_p)
+            nbytes = 4 * (V * cin + V * cout + K * cin * cout + K * V)
+            return _rows(V, cout, x.device, lambda out: _record(
+                _shape("subm_fwd/f32n", cin, cout, V), 2.0 * rules.n_rules * cin * cout, lambda: call(
+                    "msp_conv_narrow_in", ptr(xc), cin, ptr(wc), K, cout, ptr(nbr), V, ptr(out), _stream(x)), nbytes))
+        xp, wp, _, _ = _padded(x, weight)
         # flip bit 1: the weights in their own [K][c_in][c_out] layout (no transposed copy)
-        epi = None
-        if parts is not None and cout_p == cout and parts.C == cout and bn_epi_ok(rules, V, cin_p, cout_p, K):
-            epi = (parts, None, None, 0.0)
-        out = conv_tile(xp, wp, K, 2, cout_p, rules, V, "subm_fwd",
-                        2.0 * rules.n_rules * cin * cout, epi=epi)
+        out = conv_tile(xp, wp, K, 2, wp.size(2), rules, V, "subm_fwd", 2.0 * rules.n_rules * cin * cout,
+                        epi=_fwd_epi(parts, rules, V, wp, cout))
         ctx.save_for_backward(xp, wp)
-        ctx.rules, ctx.dims, ctx.narrow = rules, (cin, cout), False
-        if link is not None and cin_p == cin:
+        if link is not None and xp.size(1) == cin:
             ctx.link = link
-        return out if cout_p == cout else out[:, :cout].contiguous()
+        return _unpad_cols(out, cout).contiguous()
 
     @staticmethod
     def backward(ctx, gout):
@@ -420,33 +482,13 @@ class SubmanifoldConvFunction(torch.autograd.Function):
             return SubmanifoldConvFunction._backward_narrow(ctx, gout)
         xp, wp = ctx.saved_tensors
         rules, (cin, cout) = ctx.rules, ctx.dims
-        K, cin_p, cout_p = wp.shape
-        g = _pad_cols(gout.contiguous(), cout_p)
-        dx = dw = None
-        join = None
-        if ctx.needs_input_grad[1]:
-            V = xp.size(0)
-            dwp = None
-            rules.note_use("wgrad", cin_p, cout_p)
-            flops = 2.0 * rules.n_rules * cin * cout
-            if int(_lib.query("msp_wgrad_chunk_preferred", _lib.I64(V), K, cin_p, cout_p)) and \
-                    rules.wgrad_index(wait=True) is not None:
-                dwp, join = _on_side(xp, V, lambda: conv_wgrad_chunk(xp, g, rules, K, flops=flops))
-            if dwp is None:  # pair lists (beside the backward-data on small levels or when WGRAD_CONCURRENT)
-                p = rules.pairs  # (built by the prefetch when this batch's sizes select them: ops.prepare)
-                dwp, join = conv_wgrad_async(xp, g, p, p.pair_in, p.pair_out, K, flops)
-            dw = dwp[:, :cin, :cout].reshape(K, 1, cin, cout)
+        g = _pad_cols(gout.contiguous(), wp.size(2))
+        flops = 2.0 * rules.n_rules * cin * cout
+        dx = dw = join = None
+        if ctx.needs_input_grad[1]:  # (beside the backward-data on small levels or when WGRAD_CONCURRENT)
+            dw, join = _wgrad(rules, xp, g, wp.size(0), ctx.dims, "wgrad", flops)
         if ctx.needs_input_grad[0]:
-            V = xp.size(0)
-            link, epi = ctx.link, None
-            if link is not None and link.x is not None and bn_epi_ok(rules, V, cout_p, cin_p, K):
-                # the BatchNorm that produced x gets its backward sums from this call's epilogue
-                epi = (BnParts(cin_p, V, g.device), link.x, link.stats, link.leak)
-            dxp = conv_tile(g, wp, K, 1, cin_p, rules, V, "subm_bwd_data",
-                            2.0 * rules.n_rules * cin * cout, epi=epi)
-            if epi is not None:
-                link.bwd = (dxp, epi[0])
-            dx = dxp if cin_p == cin else dxp[:, :cin]
+            dx = _unpad_cols(_conv_tile_linked(g, wp, 1, rules, xp.size(0), ctx.link, "subm_bwd_data", flops), cin)
         if join is not None:
             join()
         ctx.link = None
@@ -460,7 +502,7 @@ class SubmanifoldConvFunction(torch.autograd.Function):
         g = gout.contiguous()
         dx = dw = None
         if ctx.needs_input_grad[1]:
-            parts = int(_lib.query("msp_conv_wgrad_narrow_parts", _lib.I64(V), K, cin, cout))
+            parts = int(_lib.query("msp_conv_wgrad_narrow_parts", V, K, cin, cout))
             slab = torch.empty((parts, K, cin, cout), dtype=torch.float32, device=x.device)
             dw = torch.empty((K, cin, cout), dtype=torch.float32, device=x.device)
             nbytes = 4 * (V * cin + V * cout + K * cin * cout + K * V)
@@ -469,9 +511,8 @@ class SubmanifoldConvFunction(torch.autograd.Function):
                 ptr(dw), _stream(x)), nbytes)
             dw = dw.reshape(K, 1, cin, cout)
         if ctx.needs_input_grad[0]:  # (the input layer's features rarely need a gradient): padded tile path
-            cin_p, cout_p = _pad16(cin), _pad16(cout)
-            wp = _pad_weight(w, cin_p, cout_p)
-            dxp = conv_tile(_pad_cols(g, cout_p), wp, K, 1, cin_p, rules, V, "subm_bwd_data",
+            wp = _pad_weight(w)
+            dxp = conv_tile(_pad_cols(g, wp.size(2)), wp, K, 1, wp.size(1), rules, V, "subm_bwd_data",
                             2.0 * rules.n_rules * cin * cout)
             dx = dxp[:, :cin]
         return dx, dw, None, None, None
@@ -485,18 +526,12 @@ class ConvolutionFunction(torch.autograd.Function):
     def forward(ctx, x, weight, rules, n_coarse, parts=None):
         """parts: BnParts for the forward sums of the output, for the BatchNorm it feeds (SubmanifoldConvFunction)."""
         _check_feats(x)
-        K, _, cin, cout = weight.shape
-        cin_p, cout_p = _pad16(cin), _pad16(cout)
-        xp = _pad_cols(x.contiguous(), cin_p)
-        wp = _pad_weight(weight.reshape(K, cin, cout), cin_p, cout_p)
-        epi = None
-        if parts is not None and cout_p == cout and parts.C == cout and \
-                bn_epi_ok(rules, n_coarse, cin_p, cout_p, K):
-            epi = (parts, None, None, 0.0)
-        out = conv_tile(xp, wp, K, 2, cout_p, rules, n_coarse, "conv_fwd", 2.0 * x.size(0) * cin * cout, epi=epi)
+        xp, wp, cin, cout = _padded(x, weight)
+        out = conv_tile(xp, wp, wp.size(0), 2, wp.size(2), rules, n_coarse, "conv_fwd", 2.0 * x.size(0) * cin * cout,
+                        epi=_fwd_epi(parts, rules, n_coarse, wp, cout))
         ctx.save_for_backward(xp, wp)
         ctx.rules, ctx.dims = rules, (cin, cout)
-        return out if cout_p == cout else out[:, :cout].contiguous()
+        return _unpad_cols(out, cout).contiguous()
 
     @staticmethod
     def backward(ctx, gout):
@@ -506,27 +541,14 @@ class ConvolutionFunction(torch.autograd.Function):
         g = _pad_cols(gout.contiguous(), cout_p)
         rules.note_use("pairs", 0, 0)
         p = rules.pairs
-        dx = dw = None
-        join = None
-        if ctx.needs_input_grad[1]:
-            flops = 2.0 * xp.size(0) * cin * cout  # one rule per fine row
-            dwp = None
-            if STRIDED_WGRAD_CHUNK:
-                # the chunk weight gradient over the child map: tiles of 128 coarse rows (dy), their children's
-                # distinct fine rows (x) staged once per tile (round 6)
-                rules.note_use("wgrad", cin_p, cout_p)
-                if int(_lib.query("msp_wgrad_chunk_preferred", _lib.I64(g.size(0)), K, cin_p, cout_p)) and \
-                        rules.wgrad_index(wait=True) is not None:
-                    dwp, join = _on_side(xp, g.size(0), lambda: conv_wgrad_chunk(xp, g, rules, K, "wgrad_strided",
-                                                                                flops))
-            if dwp is None:
-                dwp, join = conv_wgrad_async(xp, g, p, p.pair_in, p.pair_out, K, flops, "wgrad_strided")
-            dw = dwp[:, :cin, :cout].reshape(K, 1, cin, cout)
+        dx = dw = join = None
+        if ctx.needs_input_grad[1]:  # one rule per fine row; the chunk form's tiles are the coarse rows (dy)
+            dw, join = _wgrad(rules, xp, g, K, ctx.dims, "wgrad_strided", 2.0 * xp.size(0) * cin * cout,
+                              chunk=STRIDED_WGRAD_CHUNK)
         if ctx.needs_input_grad[0]:
             # dx[fine] = W[o] g[parent]: src = coarse (pair_out), dst = fine (pair_in)
-            dxp = conv_pairs(g, wp, K, cin_p, p, p.pair_out, p.pair_in, xp.size(0), "conv_bwd_data",
-                             2.0 * p.total * cin * cout)
-            dx = dxp if cin_p == cin else dxp[:, :cin]
+            dx = _unpad_cols(conv_pairs(g, wp, K, cin_p, p, p.pair_out, p.pair_in, xp.size(0), "conv_bwd_data",
+                                        2.0 * p.total * cin * cout), cin)
         if join is not None:
             join()
         return dx, dw, None, None, None
@@ -540,52 +562,29 @@ class DeconvolutionFunction(torch.autograd.Function):
     def forward(ctx, x, weight, rules, n_fine, link=None):
         """link: BnLink of the BatchNorm whose output x is (its backward sums from the backward-data's epilogue)."""
         _check_feats(x)
-        K, _, cin, cout = weight.shape
-        cin_p, cout_p = _pad16(cin), _pad16(cout)
-        xp = _pad_cols(x.contiguous(), cin_p)
-        wp = _pad_weight(weight.reshape(K, cin, cout), cin_p, cout_p)
+        xp, wp, cin, cout = _padded(x, weight)
         wt = wp.transpose(1, 2).contiguous()
         rules.note_use("pairs", 0, 0)  # the forward and both backward passes run on the pair lists
         p = rules.pairs
-        out = conv_pairs(xp, wt, K, cout_p, p, p.pair_out, p.pair_in, n_fine, "deconv_fwd", 2.0 * p.total * cin * cout)
+        out = conv_pairs(xp, wt, wp.size(0), wp.size(2), p, p.pair_out, p.pair_in, n_fine, "deconv_fwd",
+                         2.0 * p.total * cin * cout)
         ctx.save_for_backward(xp, wp)
         ctx.rules, ctx.dims = rules, (cin, cout)
-        ctx.link = link if (link is not None and cin_p == cin) else None
-        return out if cout_p == cout else out[:, :cout].contiguous()
+        ctx.link = link if (link is not None and xp.size(1) == cin) else None
+        return _unpad_cols(out, cout).contiguous()
 
     @staticmethod
     def backward(ctx, gout):
         xp, wp = ctx.saved_tensors
         rules, (cin, cout) = ctx.rules, ctx.dims
-        K, cin_p, cout_p = wp.shape
-        g = _pad_cols(gout.contiguous(), cout_p)
-        p = rules.pairs
-        dx = dw = None
-        join = None
+        g = _pad_cols(gout.contiguous(), wp.size(2))
+        flops = 2.0 * g.size(0) * cin * cout  # one rule per fine row
+        dx = dw = join = None
         if ctx.needs_input_grad[1]:
-            flops = 2.0 * g.size(0) * cin * cout  # one rule per fine row
-            dwp = None
-            if STRIDED_WGRAD_CHUNK:
-                # the chunk form over the child map with the roles swapped (the coarse input rows are the tiles'
-                # own rows, the fine output gradients the gathered ones): it gives dW^T per offset (round 6)
-                rules.note_use("wgrad", cout_p, cin_p)
-                if int(_lib.query("msp_wgrad_chunk_preferred", _lib.I64(xp.size(0)), K, cout_p, cin_p)) and \
-                        rules.wgrad_index(wait=True) is not None:
-                    dwp, join = _on_side(xp, xp.size(0), lambda: conv_wgrad_chunk(g, xp, rules, K, "wgrad_deconv",
-                                                                                 flops).transpose(1, 2))
-            if dwp is None:
-                dwp, join = conv_wgrad_async(xp, g, p, p.pair_out, p.pair_in, K, flops, "wgrad_deconv")
-            dw = dwp[:, :cin, :cout].reshape(K, 1, cin, cout)
+            dw, join = _wgrad(rules, xp, g, wp.size(0), ctx.dims, "wgrad_deconv", flops, chunk=STRIDED_WGRAD_CHUNK,
+                              transposed=True)
         if ctx.needs_input_grad[0]:
-            V = xp.size(0)
-            link, epi = ctx.link, None
-            if link is not None and link.x is not None and bn_epi_ok(rules, V, cout_p, cin_p, K):
-                epi = (BnParts(cin_p, V, g.device), link.x, link.stats, link.leak)
-            dxp = conv_tile(g, wp, K, 0, cin_p, rules, V, "deconv_bwd_data",
-                            2.0 * g.size(0) * cin * cout, epi=epi)
-            if epi is not None:
-                link.bwd = (dxp, epi[0])
-            dx = dxp if cin_p == cin else dxp[:, :cin]
+            dx = _unpad_cols(_conv_tile_linked(g, wp, 0, rules, xp.size(0), ctx.link, "deconv_bwd_data", flops), cin)
         if join is not None:
             join()
         ctx.link = None
@@ -609,6 +608,15 @@ class _IdentityPairs:
         if ar is None or ar.numel() < max(n, 1):
             ar = _ARANGE[device.index] = torch.arange(max(n, 1 << 16), dtype=torch.int32, device=device)
         self.pair = ar[:max(n, 1)]
+
+
+def _site_wgrad(x, dy, kind):
+    """x^T dy [c_in][c_out] of per-site rows (a contraction over all of them) on msp_conv_wgrad, as a one-offset
+    convolution with identity pairs."""
+    cin, cout = x.size(1), dy.size(1)
+    p = _IdentityPairs(x.size(0), x.device)
+    return conv_wgrad(_pad_cols(x, _pad16(cin)), _pad_cols(dy, _pad16(cout)), p, p.pair, p.pair, 1, kind,
+                      2.0 * p.total * cin * cout)[0, :cin, :cout]
 
 
 NIN_MAX_K = 1024  # msp_nin_gemm_ok: the split image of B's K rows must fit the kernel's LDS budget
@@ -643,7 +651,7 @@ def nin_gemm(a, b, kind="nin", keep_pad=False):
         part = torch.empty((max(M, 1), Np), dtype=torch.float32, device=a.device)
         wsb = int(_lib.query("msp_nin_gemm_workspace_size", kk, Np))
         ws = torch.empty(max(wsb // 4, 1), dtype=torch.float32, device=a.device)
-        form = "/f32" if int(_lib.query("msp_nin_gemm_form", _lib.I64(M), kk, Np)) == 1 else "/x6"
+        form = "/f32" if int(_lib.query("msp_nin_gemm_form", M, kk, Np)) == 1 else "/x6"
         _record(kind + form, flops * kk / Kp, lambda: call("msp_nin_gemm", ptr(ak), M, kk, ptr(bk), Np, ptr(part),
                                                            ptr(ws), wsb, _stream(a)), nbytes * kk // Kp)
         out = part if out is None else out.add_(part)
@@ -653,8 +661,7 @@ def nin_gemm(a, b, kind="nin", keep_pad=False):
 
 class NetworkInNetworkFunction(torch.autograd.Function):
     """out = x W (§8(a) a11).  Forward and backward-data on msp_nin_gemm (W, then W^T); the weight gradient
-    x^T dy (a contraction over all V rows) runs on msp_conv_wgrad as a one-offset convolution with identity
-    pairs."""
+    x^T dy runs on msp_conv_wgrad (_site_wgrad)."""
 
     @staticmethod
     def forward(ctx, x, weight):
@@ -671,17 +678,13 @@ class NetworkInNetworkFunction(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = nin_gemm(g, weight.t(), kind="nin_bwd_data")
         if ctx.needs_input_grad[1]:
-            cin, cout = weight.shape
-            cin_p, cout_p = _pad16(cin), _pad16(cout)
-            p = _IdentityPairs(x.size(0), x.device)
-            dw = conv_wgrad(_pad_cols(x, cin_p), _pad_cols(g, cout_p), p, p.pair, p.pair, 1, "nin_wgrad",
-                            2.0 * p.total * cin * cout)[0, :cin, :cout]
+            dw = _site_wgrad(x, g, "nin_wgrad")
         return dx, dw
 
 
 # ------------------------------------------------------------------ batch norm
 def _bn_partial_buf(V, C, device):
-    P = int(_lib.query("msp_bn_partials", _lib.I64(V), C))
+    P = int(_lib.query("msp_bn_partials", V, C))
     return torch.empty((P + 1) * 2 * C, dtype=torch.float64, device=device)
 
 
@@ -710,9 +713,27 @@ def _bn_fwd(x, weight, bias, running_mean, running_var, eps, momentum, leak, tra
     return y, stats
 
 
-def _bn_bwd(x, weight, stats, cfg, gy, addend, link=None):
+def _bn_setup(ctx, x, weight, bias, running_mean, running_var, eps, momentum, leak, train, partial, link):
+    """The forward of the BatchNorm Functions: y = BN-ReLU(x), with x (made contiguous), the weight and the
+    statistics saved for _bn_bwd, and `link` (a BnLink) filled with x and the statistics in training mode.
+    Returns (y, x)."""
+    x = x.contiguous()
+    y, stats = _bn_fwd(x, weight, bias, running_mean, running_var, eps, momentum, leak, train, partial)
+    ctx.save_for_backward(x, weight, stats)
+    ctx.cfg = (float(leak), int(train), weight is not None, bias is not None)
+    ctx.link = None
+    if link is not None and train:
+        link.x, link.stats = x, stats
+        ctx.link = link
+    return y, x
+
+
+def _bn_bwd(x, weight, stats, cfg, gy, addend, link=None, split=None):
     """dx (+ addend, fused), dweight, dbias.  link: the BnLink whose consumer's backward-data may have left this
-    BN's backward sums (used when gy is exactly the gradient that call returned)."""
+    BN's backward sums (used when gy is exactly the gradient that call returned: msp_bn_bwd_apply_cm, no
+    statistics pass).  split = (ca, need_a, need_b), never with a link: dx is written as its two column blocks
+    [V][ca], [V][C - ca] (msp_bn_bwd_apply_split) -- the gradients of the JoinTable inputs that x joined, with no
+    split pass -- and returned as the pair (ga, gb), None where not needed."""
     leak, train, has_w, has_b = cfg
     gy = gy.contiguous()
     V, C = x.shape
@@ -723,34 +744,43 @@ def _bn_bwd(x, weight, stats, cfg, gy, addend, link=None):
         link.bwd = None
         if p.written and d.data_ptr() == gy.data_ptr() and tuple(d.shape) == tuple(gy.shape) and p.C == C:
             parts = p
-    dx = torch.empty_like(x)
+    if split is None:
+        dx = torch.empty_like(x)
+        apply, outs = "msp_bn_bwd_apply_add", (ptr(dx),)
+    else:
+        ca, need_a, need_b = split
+        ga = torch.empty((V, ca), dtype=torch.float32, device=x.device)
+        gb = torch.empty((V, C - ca), dtype=torch.float32, device=x.device)
+        dx = (ga if need_a else None), (gb if need_b else None)
+        apply, outs = "msp_bn_bwd_apply_split", (ca, ptr(ga), ptr(gb))
     dw = torch.empty(C, dtype=torch.float32, device=x.device)
     db = torch.empty(C, dtype=torch.float32, device=x.device)
     add = ptr(addend) if addend is not None else None
     wp = ptr(weight) if has_w else None
-    if parts is not None:
-        # compulsory bytes: apply only (read x, dy [, shortcut grad], write dx); the sums came with dy
-        _record(_shape("bn_bwd/hbm", C, C, V), 0, lambda: call(
-            "msp_bn_bwd_apply_cm", ptr(x), ptr(gy), V, C, ptr(parts.buf), parts.P, ptr(stats), wp, leak, train, add,
-            ptr(dx), ptr(dw), ptr(db), s), 4 * V * C * (3 + (addend is not None)))
-        return dx, (dw if has_w else None), (db if has_b else None)
-    partial = _bn_partial_buf(V, C, x.device)
+    partial = _bn_partial_buf(V, C, x.device) if parts is None else None
 
     def run():
-        call("msp_bn_bwd_stats", ptr(x), ptr(gy), V, C, ptr(stats), leak, ptr(partial), s)
-        call("msp_bn_bwd_apply_add", ptr(x), ptr(gy), V, C, ptr(partial), ptr(stats), wp, leak, train, add, ptr(dx),
-             ptr(dw), ptr(db), s)
-    # compulsory bytes: statistics pass (read x, dy), apply (read x, dy [, shortcut grad], write dx)
-    _record(_shape("bn_bwd/hbm", C, C, V), 0, run, 4 * V * C * (5 + (addend is not None)))
+        if parts is not None:  # the sums came with dy: apply only
+            call("msp_bn_bwd_apply_cm", ptr(x), ptr(gy), V, C, ptr(parts.buf), parts.P, ptr(stats), wp, leak, train,
+                 add, ptr(dx), ptr(dw), ptr(db), s)
+        else:
+            call("msp_bn_bwd_stats", ptr(x), ptr(gy), V, C, ptr(stats), leak, ptr(partial), s)
+            call(apply, ptr(x), ptr(gy), V, C, ptr(partial), ptr(stats), wp, leak, train, add, *outs, ptr(dw),
+                 ptr(db), s)
+    # compulsory bytes: statistics pass (read x, dy) unless the sums came with dy, apply (read x, dy [, shortcut
+    # grad], write dx)
+    _record(_shape("bn_bwd/hbm", C, C, V), 0, run, 4 * V * C * ((5 if parts is None else 3) + (addend is not None)))
     return dx, (dw if has_w else None), (db if has_b else None)
 
 
-def _link(link, x, stats, train):
-    """The BnLink of a training-mode BN forward, filled with its input and statistics (else None)."""
-    if link is None or not train:
-        return None
-    link.x, link.stats = x, stats
-    return link
+def _split_cols(g, ca, need_a, need_b):
+    """The column blocks [V][ca], [V][C - ca] of g [V][C], each where needed (else None), in one pass."""
+    V, C = g.shape
+    ga = torch.empty((V, ca), dtype=torch.float32, device=g.device) if need_a else None
+    gb = torch.empty((V, C - ca), dtype=torch.float32, device=g.device) if need_b else None
+    if ga is not None or gb is not None:
+        call("msp_split_cols", ptr(g), V, ca, C - ca, ptr(ga), ptr(gb), _stream(g))
+    return ga, gb
 
 
 class BatchNormFunction(torch.autograd.Function):
@@ -761,12 +791,7 @@ class BatchNormFunction(torch.autograd.Function):
     def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, leak, train, partial=None,
                 link=None):
         _check_feats(x)
-        x = x.contiguous()
-        y, stats = _bn_fwd(x, weight, bias, running_mean, running_var, eps, momentum, leak, train, partial)
-        ctx.save_for_backward(x, weight, stats)
-        ctx.cfg = (float(leak), int(train), weight is not None, bias is not None)
-        ctx.link = _link(link, x, stats, train)
-        return y
+        return _bn_setup(ctx, x, weight, bias, running_mean, running_var, eps, momentum, leak, train, partial, link)[0]
 
     @staticmethod
     def backward(ctx, gy):
@@ -787,12 +812,8 @@ class BatchNormForkFunction(torch.autograd.Function):
     def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, leak, train, partial=None,
                 link=None):
         _check_feats(x)
-        x = x.contiguous()
         ctx.set_materialize_grads(False)
-        y, stats = _bn_fwd(x, weight, bias, running_mean, running_var, eps, momentum, leak, train, partial)
-        ctx.save_for_backward(x, weight, stats)
-        ctx.cfg = (float(leak), int(train), weight is not None, bias is not None)
-        ctx.link = _link(link, x, stats, train)
+        y, x = _bn_setup(ctx, x, weight, bias, running_mean, running_var, eps, momentum, leak, train, partial, link)
         return y, x.view_as(x)
 
     @staticmethod
@@ -807,42 +828,14 @@ class BatchNormForkFunction(torch.autograd.Function):
         return dx, dw, db, None, None, None, None, None, None, None, None
 
 
-def _bn_bwd_split(x, weight, stats, cfg, gy, addend, ca, need_a, need_b):
-    """_bn_bwd with dx written as its two column blocks [V][ca], [V][C - ca] (msp_bn_bwd_apply_split): the
-    gradients of the JoinTable inputs that x joined, with no split pass.  Returns (ga, gb, dweight, dbias)."""
-    leak, train, has_w, has_b = cfg
-    gy = gy.contiguous()
-    V, C = x.shape
-    s = _stream(x)
-    ga = torch.empty((V, ca), dtype=torch.float32, device=x.device)
-    gb = torch.empty((V, C - ca), dtype=torch.float32, device=x.device)
-    dw = torch.empty(C, dtype=torch.float32, device=x.device)
-    db = torch.empty(C, dtype=torch.float32, device=x.device)
-    partial = _bn_partial_buf(V, C, x.device)
-    add = ptr(addend) if addend is not None else None
-
-    def run():
-        call("msp_bn_bwd_stats", ptr(x), ptr(gy), V, C, ptr(stats), leak, ptr(partial), s)
-        call("msp_bn_bwd_apply_split", ptr(x), ptr(gy), V, C, ptr(partial), ptr(stats),
-             ptr(weight) if has_w else None, leak, train, add, ca, ptr(ga), ptr(gb), ptr(dw), ptr(db), s)
-    # compulsory bytes: statistics pass (read x, dy), apply (read x, dy [, shortcut grad], write dx's two blocks)
-    _record(_shape("bn_bwd/hbm", C, C, V), 0, run, 4 * V * C * (5 + (addend is not None)))
-    return (ga if need_a else None), (gb if need_b else None), (dw if has_w else None), (db if has_b else None)
-
-
-# The UNet decoder's JoinTable -> BatchNormalization: the BN's backward writes the join inputs' gradients itself
-# (BatchNormJoinFunction) instead of a [V][C] dx that JoinFunction's backward then splits (msp_split_cols: one read
-# and one write of V x C floats per join, 0.26 ms/step at C3).  False: JoinFunction's split, as before.
-FUSE_JOIN_SPLIT = True
-
-
 class BatchNormJoinFunction(torch.autograd.Function):
     """BatchNormFunction / BatchNormForkFunction (fork = True: the second output is x for the shortcut, whose
-    gradient is added inside the backward) over the output x = [a | b] of a JoinTable.  x comes in detached (the
-    join's forward already ran and left its statistics partials); a and b carry the gradient: the backward
-    writes d[a | b] as its two column blocks (msp_bn_bwd_apply_split), so the join's split pass is not needed.
-    The join's own autograd node receives no gradient from here; any other consumer of the joined tensor still
-    back-propagates through it (JoinFunction's split), and autograd adds the two contributions to a and b."""
+    gradient is added inside the backward) over the output x = [a | b] of a JoinTable (FUSE_JOIN_SPLIT).  x comes
+    in detached (the join's forward already ran and left its statistics partials); a and b carry the gradient:
+    the backward writes d[a | b] as its two column blocks (msp_bn_bwd_apply_split), so the join's split pass is
+    not needed.  The join's own autograd node receives no gradient from here; any other consumer of the joined
+    tensor still back-propagates through it (JoinFunction's split), and autograd adds the two contributions to a
+    and b."""
 
     @staticmethod
     def forward(ctx, x, a, b, fork, weight, bias, running_mean, running_var, eps, momentum, leak, train,
@@ -851,13 +844,9 @@ class BatchNormJoinFunction(torch.autograd.Function):
         if x.size(1) != a.size(1) + b.size(1) or x.size(0) != a.size(0):
             raise ValueError(f"BatchNormJoinFunction: x {tuple(x.shape)} is not the join of {tuple(a.shape)} and "
                              f"{tuple(b.shape)}")
-        x = x.contiguous()
         ctx.set_materialize_grads(False)
-        y, stats = _bn_fwd(x, weight, bias, running_mean, running_var, eps, momentum, leak, train, partial)
-        ctx.save_for_backward(x, weight, stats)
-        ctx.cfg = (float(leak), int(train), weight is not None, bias is not None)
         ctx.ca = a.size(1)
-        ctx.link = _link(link, x, stats, train)
+        y, x = _bn_setup(ctx, x, weight, bias, running_mean, running_var, eps, momentum, leak, train, partial, link)
         return y, x.view_as(x)
 
     @staticmethod
@@ -867,20 +856,12 @@ class BatchNormJoinFunction(torch.autograd.Function):
         if link is not None:
             link.bwd = None  # a consumer's epilogue sums are not used on this path
         need_a, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        none = (None,) * 10
         if gy is None:
-            if gx is None:
-                return (None, None, None) + none + (None,)
-            gx = gx.contiguous()
-            V, C = gx.shape
-            ga = torch.empty((V, ctx.ca), dtype=torch.float32, device=gx.device) if need_a else None
-            gb = torch.empty((V, C - ctx.ca), dtype=torch.float32, device=gx.device) if need_b else None
-            if ga is not None or gb is not None:
-                call("msp_split_cols", ptr(gx), V, ctx.ca, C - ctx.ca, ptr(ga), ptr(gb), _stream(gx))
-            return (None, ga, gb) + none + (None,)
+            ga, gb = _split_cols(gx.contiguous(), ctx.ca, need_a, need_b) if gx is not None else (None, None)
+            return (None, ga, gb) + (None,) * 11
         if gx is not None:
             gx = gx.contiguous()
-        ga, gb, dw, db = _bn_bwd_split(x, weight, stats, ctx.cfg, gy, gx, ctx.ca, need_a, need_b)
+        (ga, gb), dw, db = _bn_bwd(x, weight, stats, ctx.cfg, gy, gx, split=(ctx.ca, need_a, need_b))
         return (None, ga, gb, None, dw, db) + (None,) * 8
 
 
@@ -898,8 +879,8 @@ class ResidualJoinFunction(torch.autograd.Function):
         V, C = a.shape
         out = torch.empty_like(a)
         partial = _bn_partial_buf(V, C, a.device)
-        _record(_shape("bn_join/hbm", C, C, V), 0, lambda: call("msp_add_bn_stats", ptr(a), ptr(b), V, C, ptr(out), ptr(partial),
-                                                _stream(a)), 12 * V * C)
+        _record(_shape("bn_join/hbm", C, C, V), 0, lambda: call(
+            "msp_add_bn_stats", ptr(a), ptr(b), V, C, ptr(out), ptr(partial), _stream(a)), 12 * V * C)
         ctx.mark_non_differentiable(partial)
         ctx.set_materialize_grads(False)  # no zero-filled fp64 "gradient" of the partials per join
         return out, partial
@@ -932,7 +913,7 @@ class JoinFunction(torch.autograd.Function):
         partial = _bn_partial_buf(V, C, a.device) if stats else None
         _record(_shape("bn_join/hbm", C, C, V), 0, lambda: call(
             "msp_join_cols", ptr(a), ca, ptr(b), cb, V, ptr(out), ptr(partial), _stream(a)), 8 * V * C)
-        ctx.dims = (ca, cb)
+        ctx.ca = ca
         ctx.set_materialize_grads(False)
         if partial is not None:
             ctx.mark_non_differentiable(partial)
@@ -942,17 +923,24 @@ class JoinFunction(torch.autograd.Function):
     def backward(ctx, g, _gp):
         if g is None:
             return None, None, None
-        ca, cb = ctx.dims
-        g = g.contiguous()
-        V = g.size(0)
-        ga = torch.empty((V, ca), dtype=torch.float32, device=g.device) if ctx.needs_input_grad[0] else None
-        gb = torch.empty((V, cb), dtype=torch.float32, device=g.device) if ctx.needs_input_grad[1] else None
-        if ga is not None or gb is not None:
-            call("msp_split_cols", ptr(g), V, ca, cb, ptr(ga), ptr(gb), _stream(g))
-        return ga, gb, None
+        return (*_split_cols(g.contiguous(), ctx.ca, ctx.needs_input_grad[0], ctx.needs_input_grad[1]), None)
 
 
 # ------------------------------------------------------------------ input / output / pooling
+def _point_rows(g, rules, n_points):
+    """Voxel rows -> one row per point through the InputLayer map (msp_output_fwd)."""
+    C = g.size(1)
+    return _rows(n_points, C, g.device, lambda out: call(
+        "msp_output_fwd", ptr(g), C, ptr(rules.p2v), n_points, ptr(out), _stream(g)))
+
+
+def _voxel_sums(g, rules, n_vox):
+    """Point rows summed per voxel in the InputLayer map's fixed order (msp_output_bwd)."""
+    C = g.size(1)
+    return _rows(n_vox, C, g.device, lambda out: call(
+        "msp_output_bwd", ptr(g), C, ptr(rules.perm), ptr(rules.vstart), n_vox, ptr(out), _stream(g)))
+
+
 class InputLayerFunction(torch.autograd.Function):
     """mode 3 (sum) / 4 (mean) point -> voxel reduction (§8(a) a4)."""
 
@@ -961,28 +949,22 @@ class InputLayerFunction(torch.autograd.Function):
         _check_feats(feats)
         feats = feats.contiguous()
         C = feats.size(1)
-        s = _stream(feats)
-        out = torch.empty((max(n_vox, 1), C), dtype=torch.float32, device=feats.device)
-        if n_vox:
-            if mode == 4:
-                call("msp_input_avg_fwd", ptr(feats), C, ptr(rules.perm), ptr(rules.vstart), n_vox, ptr(out), s)
-            else:
-                call("msp_output_bwd", ptr(feats), C, ptr(rules.perm), ptr(rules.vstart), n_vox, ptr(out), s)
         ctx.rules, ctx.mode, ctx.n = rules, mode, feats.size(0)
-        return out[:n_vox]
+        if mode != 4:
+            return _voxel_sums(feats, rules, n_vox)
+        return _rows(n_vox, C, feats.device, lambda out: call(
+            "msp_input_avg_fwd", ptr(feats), C, ptr(rules.perm), ptr(rules.vstart), n_vox, ptr(out), _stream(feats)))
 
     @staticmethod
     def backward(ctx, g):
         g = g.contiguous()
         rules = ctx.rules
         C = g.size(1)
-        df = torch.empty((max(ctx.n, 1), C), dtype=torch.float32, device=g.device)
-        if ctx.n:
-            if ctx.mode == 4:
-                call("msp_input_avg_bwd", ptr(g), C, ptr(rules.p2v), ptr(rules.vstart), ctx.n, ptr(df), _stream(g))
-            else:
-                call("msp_output_fwd", ptr(g), C, ptr(rules.p2v), ctx.n, ptr(df), _stream(g))
-        return df[:ctx.n], None, None, None
+        if ctx.mode != 4:
+            return _point_rows(g, rules, ctx.n), None, None, None
+        return _rows(ctx.n, C, g.device, lambda df: call(
+            "msp_input_avg_bwd", ptr(g), C, ptr(rules.p2v), ptr(rules.vstart), ctx.n, ptr(df), _stream(g))), \
+            None, None, None
 
 
 class OutputLayerFunction(torch.autograd.Function):
@@ -992,22 +974,12 @@ class OutputLayerFunction(torch.autograd.Function):
     def forward(ctx, x, rules):
         _check_feats(x)
         x = x.contiguous()
-        C = x.size(1)
-        out = torch.empty((max(rules.n_points, 1), C), dtype=torch.float32, device=x.device)
-        if rules.n_points:
-            call("msp_output_fwd", ptr(x), C, ptr(rules.p2v), rules.n_points, ptr(out), _stream(x))
         ctx.rules, ctx.V = rules, x.size(0)
-        return out[:rules.n_points]
+        return _point_rows(x, rules, rules.n_points)
 
     @staticmethod
     def backward(ctx, g):
-        g = g.contiguous()
-        rules = ctx.rules
-        C = g.size(1)
-        din = torch.empty((max(ctx.V, 1), C), dtype=torch.float32, device=g.device)
-        if ctx.V:
-            call("msp_output_bwd", ptr(g), C, ptr(rules.perm), ptr(rules.vstart), ctx.V, ptr(din), _stream(g))
-        return din[:ctx.V], None
+        return _voxel_sums(g.contiguous(), ctx.rules, ctx.V), None
 
 
 class SceneMeanFunction(torch.autograd.Function):
@@ -1024,7 +996,7 @@ class SceneMeanFunction(torch.autograd.Function):
         vscene = torch.empty(B + 1, dtype=torch.int64, device=dev)
         npts = torch.empty(B, dtype=torch.int64, device=dev)
         out = torch.empty((B, C), dtype=torch.float32, device=dev)
-        wsb = int(_lib.query("msp_scene_mean_workspace_size", _lib.I64(V), B, C))
+        wsb = int(_lib.query("msp_scene_mean_workspace_size", V, B, C))
         ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
         shift = 3 * level.log2
         call("msp_scene_mean_fwd", ptr(x), C, ptr(level.keys), V, shift, ptr(rules.vstart), B, ptr(vscene),
@@ -1042,10 +1014,9 @@ class SceneMeanFunction(torch.autograd.Function):
             return None, None, None, None
         g = g.contiguous()
         C = g.size(1)
-        dx = torch.empty((max(ctx.V, 1), C), dtype=torch.float32, device=g.device)
-        call("msp_scene_mean_bwd", ptr(g), C, ptr(ctx.level.keys), ctx.V, ctx.shift, ptr(ctx.rules.vstart),
-             ptr(npts), ptr(dx), _stream(g))
-        return dx[:ctx.V], None, None, None
+        return _rows(ctx.V, C, g.device, lambda dx: call(
+            "msp_scene_mean_bwd", ptr(g), C, ptr(ctx.level.keys), ctx.V, ctx.shift, ptr(ctx.rules.vstart),
+            ptr(npts), ptr(dx), _stream(g)), guard=True), None, None, None
 
 
 class PointLogitsFunction(torch.autograd.Function):
@@ -1065,33 +1036,21 @@ class PointLogitsFunction(torch.autograd.Function):
         if weight.size(1) != C:
             raise ValueError(f"PointLogits: Linear({weight.size(1)}, {n_out}) on {C} channels")
         vl = nin_gemm(x, weight.t(), kind="logits_fwd", keep_pad=True)  # (V, pad16(n_out))
-        out = torch.empty((max(rules.n_points, 1), n_out), dtype=torch.float32, device=x.device)
-        if rules.n_points:
-            call("msp_point_rows_bias", ptr(vl), vl.size(1), n_out, ptr(bias.contiguous()) if bias is not None
-                 else None, ptr(rules.p2v), rules.n_points, ptr(out), _stream(x))
         ctx.save_for_backward(x, weight)
         ctx.rules, ctx.has_bias = rules, bias is not None
-        return out[:rules.n_points]
+        return _rows(rules.n_points, n_out, x.device, lambda out: call(
+            "msp_point_rows_bias", ptr(vl), vl.size(1), n_out, ptr(bias.contiguous()) if bias is not None else None,
+            ptr(rules.p2v), rules.n_points, ptr(out), _stream(x)))
 
     @staticmethod
     def backward(ctx, g):
         x, weight = ctx.saved_tensors
-        rules = ctx.rules
-        V, C = x.shape
-        n_out = weight.size(0)
-        g = g.contiguous()
-        gv = torch.empty((max(V, 1), n_out), dtype=torch.float32, device=g.device)
-        if V:
-            call("msp_output_bwd", ptr(g), n_out, ptr(rules.perm), ptr(rules.vstart), V, ptr(gv), _stream(g))
-        gv = gv[:V]
+        gv = _voxel_sums(g.contiguous(), ctx.rules, x.size(0))
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = nin_gemm(gv, weight, kind="logits_bwd_data")
         if ctx.needs_input_grad[1]:
-            cin_p, cout_p = _pad16(C), _pad16(n_out)
-            p = _IdentityPairs(V, x.device)
-            dw = conv_wgrad(_pad_cols(x, cin_p), _pad_cols(gv, cout_p), p, p.pair, p.pair, 1, "logits_wgrad",
-                            2.0 * V * C * n_out)[0, :C, :n_out].t()
+            dw = _site_wgrad(x, gv, "logits_wgrad").t()
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = gv.sum(0)
         return dx, dw, db, None
@@ -1196,7 +1155,7 @@ class PointCrossEntropyFunction(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=dev)
         nums = torch.empty(2, dtype=torch.int64, device=dev)
         lse = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
-        wsb = int(_lib.query("msp_point_ce_workspace_size", _lib.I64(N)))
+        wsb = int(_lib.query("msp_point_ce_workspace_size", N))
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
         call("msp_point_ce_fwd", ptr(logits), N, C, ptr(labels), ptr(loss), ptr(nums), ptr(nums[1:]), ptr(lse),
              ptr(ws), wsb, _stream(logits))
@@ -1222,20 +1181,16 @@ class UnPoolingFunction(torch.autograd.Function):
         _check_feats(x)
         x = x.contiguous()
         C = x.size(1)
-        out = torch.empty((max(n_fine, 1), C), dtype=torch.float32, device=x.device)
-        if n_fine:
-            call("msp_unpool_fwd", ptr(x), C, ptr(rules.parent_of), n_fine, ptr(out), _stream(x))
         ctx.rules, ctx.Vc = rules, x.size(0)
-        return out[:n_fine]
+        return _rows(n_fine, C, x.device, lambda out: call(
+            "msp_unpool_fwd", ptr(x), C, ptr(rules.parent_of), n_fine, ptr(out), _stream(x)))
 
     @staticmethod
     def backward(ctx, g):
         g = g.contiguous()
         C = g.size(1)
-        din = torch.empty((max(ctx.Vc, 1), C), dtype=torch.float32, device=g.device)
-        if ctx.Vc:
-            call("msp_unpool_bwd", ptr(g), C, ptr(ctx.rules.child_start), ctx.Vc, ptr(din), _stream(g))
-        return din[:ctx.Vc], None, None
+        return _rows(ctx.Vc, C, g.device, lambda din: call(
+            "msp_unpool_bwd", ptr(g), C, ptr(ctx.rules.child_start), ctx.Vc, ptr(din), _stream(g))), None, None
 
 
 class MaxPoolingFunction(torch.autograd.Function):
@@ -1244,13 +1199,11 @@ class MaxPoolingFunction(torch.autograd.Function):
         _check_feats(x)
         x = x.contiguous()
         C = x.size(1)
-        out = torch.empty((max(n_coarse, 1), C), dtype=torch.float32, device=x.device)
         arg = torch.empty((max(n_coarse, 1), C), dtype=torch.int32, device=x.device)
-        if n_coarse:
-            call("msp_maxpool_fwd", ptr(x), C, ptr(rules.child_start), n_coarse, ptr(out), ptr(arg), _stream(x))
         ctx.save_for_backward(arg)
         ctx.Vf, ctx.Vc = x.size(0), n_coarse
-        return out[:n_coarse]
+        return _rows(n_coarse, C, x.device, lambda out: call(
+            "msp_maxpool_fwd", ptr(x), C, ptr(rules.child_start), n_coarse, ptr(out), ptr(arg), _stream(x)))
 
     @staticmethod
     def backward(ctx, g):

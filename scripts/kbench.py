@@ -85,8 +85,6 @@ def conv_forms(rules, V, cin, cout):
             return f
         for v in [int(t) for t in os.environ.get("EXP_VARIANTS", "10,11").split(",") if t]:
             forms[f"x6s_v{v}"] = exp(v)
-    if hasattr(ops, "conv_unit") and cout <= 64:
-        forms["unit"] = lambda x, wt, flip: ops.conv_unit(x, wt, 27, flip, cout, rules, V)
     if FORMS:
         forms = {k: v for k, v in forms.items() if k in FORMS.split(",")}
     return forms
@@ -240,8 +238,6 @@ def main():
                     fs["chunk"] = lambda: ops.conv_wgrad_chunk(x, dy, rules, 27)
                 if WFORMS:
                     fs = {k: v for k, v in fs.items() if k in WFORMS.split(",")}
-                if hasattr(ops, "conv_wgrad_unit"):
-                    fs["unit"] = lambda: ops.conv_wgrad_unit(x, dy, rules, 27)
                 res = []
                 for name, f in fs.items():
                     try:
