@@ -17,9 +17,22 @@
 // keep = 0 <= p < full_scale, coordinate = trunc(p).  min/max are exact, so
 // the atomic combination is order-independent; the compaction keeps the
 // point order (block prefix sums), so the output is deterministic.
+//
+// Subcloud training (`label: subcloud`, data.py:69-125): a sample is the ball
+// of radius in_radius around an anchor of a scene, not the scene.  The balls
+// are never materialised: msp_merge_ball runs the same kernels with sample b
+// reading scene scene_of[b] and the membership test
+//   d2 = ((dx*dx + dy*dy) + dz*dz) <= r2,  dx = double(x) - centre_x
+// (fp64, every product and sum rounded separately) fused into the three
+// passes that read the points (min/max, count, stable write).  The kernels
+// are templates on kBall; msp_merge instantiates kBall = false, in which the
+// predicate is no code at all.  msp_ball_count counts the members of every
+// anchor of every scene in one launch (integer LDS + global atomics: exact,
+// order-independent); the host keeps the anchors with >= min_points members.
 #include "msp_common.h"
 
 #include <climits>
+#include <cmath>
 
 #pragma clang fp contract(off)
 
@@ -37,6 +50,41 @@ struct MergeParams {
   const double* u2;    // [B][3]
   const float* shift;  // [B][3]  colour shift
 };
+
+// The ball of sample b (kBall only): the scene it is cut from, its centre, the squared radius.
+struct BallParams {
+  const int* scene_of;   // [B]
+  const double* centre;  // [B][3]
+  double r2;
+};
+
+// One rounding per product and per sum.  Written with plain operators under this file's `fp contract(off)`:
+// the toolchain's __dmul_rn / __dadd_rn are inline functions of a header compiled under its own contraction
+// setting, and a product of theirs that feeds a sum is fused into one FMA.  A member test on the ball's surface
+// must not depend on that, so the distance uses these.
+__device__ inline double mul_rn(double a, double b) { return a * b; }
+__device__ inline double add_rn(double a, double b) { return a + b; }
+
+// query_radius' reduced-distance test for the Euclidean metric, in the restatement's evaluation order
+__device__ inline bool in_ball(double x, double y, double z, double cx, double cy, double cz, double r2) {
+  const double dx = add_rn(x, -cx), dy = add_rn(y, -cy), dz = add_rn(z, -cz);
+  return add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz)) <= r2;
+}
+
+template <bool kBall>
+__device__ inline int sample_scene(const BallParams& Q, int b) {
+  if constexpr (kBall) return Q.scene_of[b];
+  else return b;
+}
+
+template <bool kBall>
+__device__ inline bool member(const float* __restrict__ xyz, int64_t i, const BallParams& Q, int b) {
+  if constexpr (kBall)
+    return in_ball((double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], Q.centre[3 * b],
+                   Q.centre[3 * b + 1], Q.centre[3 * b + 2], Q.r2);
+  else
+    return true;
+}
 
 // order-preserving map of doubles onto int64 (for atomic min / max)
 __device__ inline long long ord_of(double d) {
@@ -65,16 +113,17 @@ __device__ inline void transform(const float* __restrict__ xyz, int64_t i, const
   }
 }
 
+template <bool kBall>
 __global__ __launch_bounds__(kMT) void merge_minmax_kernel(const float* __restrict__ xyz,
                                                            const int64_t* __restrict__ sstart, MergeParams P,
-                                                           long long* __restrict__ mm /*[B][6]*/) {
+                                                           BallParams Q, long long* __restrict__ mm /*[B][6]*/) {
   __shared__ long long red[6][kMT / 64];
-  const int b = blockIdx.y;
-  const int64_t s0 = sstart[b], s1 = sstart[b + 1];
+  const int b = blockIdx.y, sc = sample_scene<kBall>(Q, b);
+  const int64_t s0 = sstart[sc], s1 = sstart[sc + 1];
   long long lo[3] = {LLONG_MAX, LLONG_MAX, LLONG_MAX}, hi[3] = {LLONG_MIN, LLONG_MIN, LLONG_MIN};
   for (int k = 0; k < kMIt; ++k) {
     const int64_t i = s0 + (int64_t)blockIdx.x * kMPB + k * kMT + threadIdx.x;
-    if (i < s1) {
+    if (i < s1 && member<kBall>(xyz, i, Q, b)) {
       double t[3];
       transform(xyz, i, P.rot + 9 * b, P.c1 + 3 * b, P.c2 + 3 * b, t);
 #pragma unroll
@@ -116,6 +165,10 @@ __global__ void merge_offset_kernel(const long long* __restrict__ mm, int B, dou
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= 3 * B) return;
   const int b = e / 3, j = e % 3;
+  if (mm[6 * b + j] > mm[6 * b + 3 + j]) {  // no point touched the identities (empty scene or ball): no NaN offset
+    offset[e] = 0.0;
+    return;
+  }
   const double m = dbl_of(mm[6 * b + j]), M = dbl_of(mm[6 * b + 3 + j]);
   double q1, q2;
   if (mode == 0) {
@@ -146,17 +199,18 @@ __device__ inline bool kept(const float* __restrict__ xyz, int64_t i, int b, con
 }
 
 // counts[b * nbx + bx] = kept points of block (b, bx)
+template <bool kBall>
 __global__ __launch_bounds__(kMT) void merge_count_kernel(const float* __restrict__ xyz,
                                                           const int64_t* __restrict__ sstart, MergeParams P,
-                                                          const double* __restrict__ offset, double fs,
+                                                          BallParams Q, const double* __restrict__ offset, double fs,
                                                           int64_t* __restrict__ counts) {
-  const int b = blockIdx.y;
-  const int64_t s0 = sstart[b], s1 = sstart[b + 1];
+  const int b = blockIdx.y, sc = sample_scene<kBall>(Q, b);
+  const int64_t s0 = sstart[sc], s1 = sstart[sc + 1];
   int64_t c = 0;
   for (int k = 0; k < kMIt; ++k) {
     const int64_t i = s0 + (int64_t)blockIdx.x * kMPB + k * kMT + threadIdx.x;
     double p[3];
-    if (i < s1 && kept(xyz, i, b, P, offset, fs, p)) ++c;
+    if (i < s1 && member<kBall>(xyz, i, Q, b) && kept(xyz, i, b, P, offset, fs, p)) ++c;
   }
   int64_t tot;
   block_excl_scan<kMT>(c, &tot);
@@ -165,23 +219,24 @@ __global__ __launch_bounds__(kMT) void merge_count_kernel(const float* __restric
 
 // stable compaction: output position = block start + prefix of the kept
 // points in point order (thread-major inside each of the kMIt sweeps)
+template <bool kBall>
 __global__ __launch_bounds__(kMT) void merge_write_kernel(const float* __restrict__ xyz,
                                                           const float* __restrict__ rgb,
                                                           const int64_t* __restrict__ lab_in,
                                                           const int64_t* __restrict__ sstart, MergeParams P,
-                                                          const double* __restrict__ offset, double fs,
+                                                          BallParams Q, const double* __restrict__ offset, double fs,
                                                           const int64_t* __restrict__ starts,
                                                           int64_t* __restrict__ coords, float* __restrict__ feats,
                                                           int64_t* __restrict__ lab_out, int64_t* __restrict__ ids,
                                                           int64_t id_base, unsigned* __restrict__ label_mask) {
-  const int b = blockIdx.y;
-  const int64_t s0 = sstart[b], s1 = sstart[b + 1];
+  const int b = blockIdx.y, sc = sample_scene<kBall>(Q, b);
+  const int64_t s0 = sstart[sc], s1 = sstart[sc + 1];
   int64_t pos = starts[(int64_t)b * gridDim.x + blockIdx.x];
   unsigned mask = 0;
   for (int k = 0; k < kMIt; ++k) {
     const int64_t i = s0 + (int64_t)blockIdx.x * kMPB + k * kMT + threadIdx.x;
     double p[3];
-    const bool keep = i < s1 && kept(xyz, i, b, P, offset, fs, p);
+    const bool keep = i < s1 && member<kBall>(xyz, i, Q, b) && kept(xyz, i, b, P, offset, fs, p);
     int64_t tot;
     const int64_t e = pos + block_excl_scan<kMT>((int64_t)keep, &tot);
     if (keep) {
@@ -222,6 +277,95 @@ __global__ void merge_finish_kernel(const int64_t* __restrict__ starts, int nbx,
   }
 }
 
+// ---- msp_ball_count: members of every anchor's ball, all scenes in one launch ------------------------------
+// Block (bx, scene) holds kMPB points of the scene in registers and walks the scene's anchors in chunks of kBC
+// centres staged in LDS, so any anchor count works.  Per anchor the block's members are counted with wave
+// ballots, combined over the waves with an LDS integer atomic and over the blocks with one global integer
+// atomic per (block, anchor with members): exact and independent of the order.
+constexpr int kBC = 256;
+
+__global__ void ball_zero_kernel(const int64_t* __restrict__ astart, int n_scenes,
+                                 unsigned long long* __restrict__ counts) {
+  const int64_t A = astart[n_scenes];
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < A; e += (int64_t)gridDim.x * blockDim.x)
+    counts[e] = 0ull;
+}
+
+__global__ __launch_bounds__(kMT) void ball_count_kernel(const float* __restrict__ xyz,
+                                                         const int64_t* __restrict__ sstart,
+                                                         const double* __restrict__ centres,
+                                                         const int64_t* __restrict__ astart, double r2,
+                                                         unsigned long long* __restrict__ counts) {
+  __shared__ double cen[3 * kBC];
+  __shared__ unsigned cnt[kBC];
+  const int sc = blockIdx.y;
+  const int64_t s1 = sstart[sc + 1], base = sstart[sc] + (int64_t)blockIdx.x * kMPB;
+  if (base >= s1) return;  // block-uniform: a scene shorter than the longest one
+  double p[kMIt][3];
+  bool live[kMIt];
+#pragma unroll
+  for (int k = 0; k < kMIt; ++k) {
+    const int64_t i = base + k * kMT + threadIdx.x;
+    live[k] = i < s1;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) p[k][j] = live[k] ? (double)xyz[3 * i + j] : 0.0;
+  }
+  const int64_t a1 = astart[sc + 1];
+  for (int64_t c0 = astart[sc]; c0 < a1; c0 += kBC) {
+    const int nc = (int)(a1 - c0 < kBC ? a1 - c0 : kBC);
+    for (int e = threadIdx.x; e < 3 * nc; e += kMT) cen[e] = centres[3 * c0 + e];
+    for (int e = threadIdx.x; e < nc; e += kMT) cnt[e] = 0u;
+    __syncthreads();
+    for (int a = 0; a < nc; ++a) {
+      const double cx = cen[3 * a], cy = cen[3 * a + 1], cz = cen[3 * a + 2];
+      unsigned n = 0;
+#pragma unroll
+      for (int k = 0; k < kMIt; ++k)
+        n += (unsigned)__popcll(ballot64(live[k] && in_ball(p[k][0], p[k][1], p[k][2], cx, cy, cz, r2)));
+      if (lane_id() == 0 && n) atomicAdd(&cnt[a], n);
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < nc; e += kMT)
+      if (cnt[e]) atomicAdd(&counts[c0 + e], (unsigned long long)cnt[e]);
+    __syncthreads();  // cen / cnt are rewritten by the next chunk
+  }
+}
+
+// The launches of msp_merge (kBall = false) and msp_merge_ball (kBall = true); arguments already validated.
+template <bool kBall>
+int merge_launch(const char* what, const float* xyz, const float* rgb, const int64_t* labels,
+                 const int64_t* scene_start, int B, int64_t max_scene_points, int mode, double full_scale,
+                 MergeParams P, BallParams Q, int n_classes, int64_t* coords, float* feats, int64_t* labels_out,
+                 int64_t* point_ids, int64_t point_id_base, int64_t* batch_offsets, float* scene_labels, void* ws,
+                 hipStream_t s) {
+  const int64_t nbx = ceil_div(max_scene_points > 0 ? max_scene_points : 1, kMPB);
+  const int64_t m = (int64_t)B * nbx;
+  char* w = static_cast<char*>(ws);
+  long long* mm = reinterpret_cast<long long*>(w);
+  w += (size_t)B * 6 * sizeof(long long);
+  double* offset = reinterpret_cast<double*>(w);
+  w += (size_t)B * 3 * sizeof(double);
+  unsigned* label_mask = reinterpret_cast<unsigned*>(w);
+  w += ((size_t)B * sizeof(unsigned) + 7) / 8 * 8;
+  int64_t* counts = reinterpret_cast<int64_t*>(w);
+  int64_t* starts = counts + m;
+  int64_t* total = starts + m;
+  void* sws = total + 1;
+  merge_init_kernel<<<(unsigned)ceil_div(6 * B, 256), 256, 0, s>>>(mm, label_mask, B);
+  const dim3 grid((unsigned)nbx, (unsigned)B);
+  merge_minmax_kernel<kBall><<<grid, kMT, 0, s>>>(xyz, scene_start, P, Q, mm);
+  merge_offset_kernel<<<(unsigned)ceil_div(3 * B, 64), 64, 0, s>>>(mm, B, full_scale, mode, P, offset);
+  merge_count_kernel<kBall><<<grid, kMT, 0, s>>>(xyz, scene_start, P, Q, offset, full_scale, counts);
+  int rc = scan_exclusive_i64(counts, starts, m, total, sws, scan_ws_bytes(m), s);
+  if (rc) return rc;
+  merge_write_kernel<kBall><<<grid, kMT, 0, s>>>(xyz, rgb, labels, scene_start, P, Q, offset, full_scale, starts,
+                                                 coords, feats, labels_out, point_ids, point_id_base, label_mask);
+  const int nf = (B + 1) > B * n_classes ? B + 1 : B * n_classes;
+  merge_finish_kernel<<<(unsigned)ceil_div(nf, 256), 256, 0, s>>>(starts, (int)nbx, B, total, label_mask,
+                                                                  n_classes, batch_offsets, scene_labels);
+  return check_launch(what);
+}
+
 }  // namespace msp
 
 using namespace msp;
@@ -244,34 +388,49 @@ int msp_merge(const float* xyz, const float* rgb, const int64_t* labels, const i
                   n_classes <= 32,
               "msp_merge: bad arguments (B=%d mode=%d n_classes=%d)", B, mode, n_classes);
   MSP_REQUIRE(ws_bytes >= msp_merge_workspace_size(B, max_scene_points), "msp_merge: workspace too small");
+  return merge_launch<false>("msp_merge", xyz, rgb, labels, scene_start, B, max_scene_points, mode, full_scale,
+                             MergeParams{rot, c1, c2, u1, u2, shift}, BallParams{nullptr, nullptr, 0.0}, n_classes,
+                             coords, feats, labels_out, point_ids, point_id_base, batch_offsets, scene_labels, ws,
+                             as_stream(stream));
+}
+
+size_t msp_merge_ball_workspace_size(int B, int64_t max_scene_points) {
+  return msp_merge_workspace_size(B, max_scene_points);
+}
+
+int msp_merge_ball(const float* xyz, const float* rgb, const int64_t* labels, const int64_t* scene_start, int B,
+                   int64_t max_scene_points, int mode, double full_scale, const double* rot, const double* c1,
+                   const double* c2, const double* u1, const double* u2, const float* shift, int n_classes,
+                   int64_t* coords, float* feats, int64_t* labels_out, int64_t* point_ids, int64_t point_id_base,
+                   int64_t* batch_offsets, float* scene_labels, void* ws, size_t ws_bytes, const int* scene_of,
+                   const double* centre, double r2, msp_stream_t stream) {
+  MSP_REQUIRE(B >= 1 && B <= 65535 && max_scene_points >= 0 && full_scale > 0 && n_classes >= 0,
+              "msp_merge_ball: bad arguments (B=%d max_scene_points=%lld)", B, (long long)max_scene_points);
+  MSP_REQUIRE(mode == 0, "msp_merge_ball: mode %d (only 0, train, is built)", mode);
+  MSP_REQUIRE(n_classes <= 32, "msp_merge_ball: n_classes=%d exceeds the 32-bit class mask", n_classes);
+  MSP_REQUIRE(r2 > 0 && std::isfinite(r2), "msp_merge_ball: r2 must be positive and finite (got %g)", r2);
+  MSP_REQUIRE(scene_of && centre, "msp_merge_ball: scene_of and centre must not be null");
+  MSP_REQUIRE(ws_bytes >= msp_merge_ball_workspace_size(B, max_scene_points), "msp_merge_ball: workspace too small");
+  return merge_launch<true>("msp_merge_ball", xyz, rgb, labels, scene_start, B, max_scene_points, mode, full_scale,
+                            MergeParams{rot, c1, c2, u1, u2, shift}, BallParams{scene_of, centre, r2}, n_classes,
+                            coords, feats, labels_out, point_ids, point_id_base, batch_offsets, scene_labels, ws,
+                            as_stream(stream));
+}
+
+int msp_ball_count(const float* xyz, const int64_t* scene_start, int n_scenes, int64_t max_scene_points,
+                   const double* centres, const int64_t* anchor_start, double r2, int64_t* counts,
+                   msp_stream_t stream) {
+  MSP_REQUIRE(n_scenes >= 1 && n_scenes <= 65535 && max_scene_points >= 0,
+              "msp_ball_count: bad arguments (n_scenes=%d max_scene_points=%lld)", n_scenes,
+              (long long)max_scene_points);
+  MSP_REQUIRE(r2 > 0 && std::isfinite(r2), "msp_ball_count: r2 must be positive and finite (got %g)", r2);
+  MSP_REQUIRE(xyz && scene_start && centres && anchor_start && counts, "msp_ball_count: null argument");
   hipStream_t s = as_stream(stream);
-  const int64_t nbx = ceil_div(max_scene_points > 0 ? max_scene_points : 1, kMPB);
-  const int64_t m = (int64_t)B * nbx;
-  char* w = static_cast<char*>(ws);
-  long long* mm = reinterpret_cast<long long*>(w);
-  w += (size_t)B * 6 * sizeof(long long);
-  double* offset = reinterpret_cast<double*>(w);
-  w += (size_t)B * 3 * sizeof(double);
-  unsigned* label_mask = reinterpret_cast<unsigned*>(w);
-  w += ((size_t)B * sizeof(unsigned) + 7) / 8 * 8;
-  int64_t* counts = reinterpret_cast<int64_t*>(w);
-  int64_t* starts = counts + m;
-  int64_t* total = starts + m;
-  void* sws = total + 1;
-  merge_init_kernel<<<(unsigned)ceil_div(6 * B, 256), 256, 0, s>>>(mm, label_mask, B);
-  MergeParams P{rot, c1, c2, u1, u2, shift};
-  const dim3 grid((unsigned)nbx, (unsigned)B);
-  merge_minmax_kernel<<<grid, kMT, 0, s>>>(xyz, scene_start, P, mm);
-  merge_offset_kernel<<<(unsigned)ceil_div(3 * B, 64), 64, 0, s>>>(mm, B, full_scale, mode, P, offset);
-  merge_count_kernel<<<grid, kMT, 0, s>>>(xyz, scene_start, P, offset, full_scale, counts);
-  int rc = scan_exclusive_i64(counts, starts, m, total, sws, scan_ws_bytes(m), s);
-  if (rc) return rc;
-  merge_write_kernel<<<grid, kMT, 0, s>>>(xyz, rgb, labels, scene_start, P, offset, full_scale, starts, coords, feats,
-                                          labels_out, point_ids, point_id_base, label_mask);
-  const int nf = (B + 1) > B * n_classes ? B + 1 : B * n_classes;
-  merge_finish_kernel<<<(unsigned)ceil_div(nf, 256), 256, 0, s>>>(starts, (int)nbx, B, total, label_mask,
-                                                                  n_classes, batch_offsets, scene_labels);
-  return check_launch("msp_merge");
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
+  ball_zero_kernel<<<256, 256, 0, s>>>(anchor_start, n_scenes, out);
+  const dim3 grid((unsigned)ceil_div(max_scene_points > 0 ? max_scene_points : 1, kMPB), (unsigned)n_scenes);
+  ball_count_kernel<<<grid, kMT, 0, s>>>(xyz, scene_start, centres, anchor_start, r2, out);
+  return check_launch("msp_ball_count");
 }
 
 }  // extern "C"

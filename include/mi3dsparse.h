@@ -554,6 +554,36 @@ int msp_merge(const float* xyz, const float* rgb, const int64_t* labels, const i
               int64_t* coords, float* feats, int64_t* labels_out, int64_t* point_ids, int64_t point_id_base,
               int64_t* batch_offsets, float* scene_labels, void* ws, size_t ws_bytes, msp_stream_t stream);
 
+/* Subcloud training batches (`label: subcloud`, dataset/data.py:69-125, additive in ABI 10): a sample is the ball
+ * of squared radius r2 around a centre inside a scene; the balls are never materialised.  Point i is a member of
+ * the ball of centre c when ((dx*dx + dy*dy) + dz*dz) <= r2 with dx = double(x_i) - c_x, every product and sum
+ * rounded separately in fp64 (query_radius' reduced-distance test; the point at distance exactly r is a member).
+ *
+ * msp_ball_count: counts[a] = members of anchor a, for the anchors [anchor_start[s], anchor_start[s+1]) of every
+ * scene s (centres[A][3] f64, anchor_start[n_scenes+1] int64, both on the device; A = anchor_start[n_scenes]),
+ * tested against the points of scene s only.  One launch over all scenes' points; counts[A] (int64) is zeroed
+ * inside the call; integer atomics, so the result is exact and independent of the order.  n_scenes <= 65535.
+ *
+ * msp_merge_ball: msp_merge (mode 0 only) for B samples where sample b is the ball (scene_of[b], centre[b][3],
+ * r2): it reads the points of scene scene_of[b] (int32, device; each value must be a valid scene of scene_start;
+ * the same scene may appear several times) and applies the membership test ahead of everything else, so the
+ * min/max, the offset, the crop, the labels and the batch column (= b) are the ball's.  Members keep ascending
+ * point order.  max_scene_points bounds the scenes that scene_of names.  point_ids (may be NULL) = point_id_base
+ * + index into xyz.  A ball without members is harmless: zero rows, batch_offsets[b+1] == batch_offsets[b], an
+ * all-zero scene_labels row.  Output capacity: the sum of the samples' member counts.  Rejected before any HIP
+ * call: B < 1, mode != 0, r2 <= 0 or non-finite, NULL scene_of / centre, n_classes > 32,
+ * ws_bytes < msp_merge_ball_workspace_size(B, max_scene_points). */
+int msp_ball_count(const float* xyz, const int64_t* scene_start, int n_scenes, int64_t max_scene_points,
+                   const double* centres, const int64_t* anchor_start, double r2, int64_t* counts,
+                   msp_stream_t stream);
+size_t msp_merge_ball_workspace_size(int B, int64_t max_scene_points);
+int msp_merge_ball(const float* xyz, const float* rgb, const int64_t* labels, const int64_t* scene_start, int B,
+                   int64_t max_scene_points, int mode, double full_scale, const double* rot, const double* c1,
+                   const double* c2, const double* u1, const double* u2, const float* shift, int n_classes,
+                   int64_t* coords, float* feats, int64_t* labels_out, int64_t* point_ids, int64_t point_id_base,
+                   int64_t* batch_offsets, float* scene_labels, void* ws, size_t ws_bytes, const int* scene_of,
+                   const double* centre, double r2, msp_stream_t stream);
+
 /* The training step's optimizer (round 6, ABI 10): torch.optim.Adam (the reference's train.py:39, Adam(lr=1e-3);
  * amsgrad off) over up to MSP_ADAM_MAX_TENSORS parameter tensors in one launch.  table: device array of n
  * msp_adam_tensor (param, exp_avg, exp_avg_sq: fp32, n floats each, contiguous); chunk_start: device exclusive
