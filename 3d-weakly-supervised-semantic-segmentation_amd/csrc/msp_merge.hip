@@ -29,89 +29,15 @@
 // predicate is no code at all.  msp_ball_count counts the members of every
 // anchor of every scene in one launch (integer LDS + global atomics: exact,
 // order-independent); the host keeps the anchors with >= min_points members.
-#include "msp_common.h"
-
-#include <climits>
-#include <cmath>
+//
+// Elastic distortion (msp_elastic.hip: msp_merge_elastic) displaces t before the placement and leaves it in a
+// workspace D; the count and write kernels are templates on kElastic as well and then load t from D instead of
+// transforming.  msp_merge and msp_merge_ball instantiate kElastic = false, in which D is never touched.
+#include "msp_merge.h"
 
 #pragma clang fp contract(off)
 
 namespace msp {
-
-constexpr int kMT = 256;
-constexpr int kMIt = 4;  // points per thread
-constexpr int kMPB = kMT * kMIt;
-
-struct MergeParams {
-  const double* rot;   // [B][9]  row-major 3x3 (points are row vectors: t = a . rot)
-  const double* c1;    // [B][3]
-  const double* c2;    // [B][3]
-  const double* u1;    // [B][3]  the two rand(3) draws of the offset
-  const double* u2;    // [B][3]
-  const float* shift;  // [B][3]  colour shift
-};
-
-// The ball of sample b (kBall only): the scene it is cut from, its centre, the squared radius.
-struct BallParams {
-  const int* scene_of;   // [B]
-  const double* centre;  // [B][3]
-  double r2;
-};
-
-// One rounding per product and per sum.  Written with plain operators under this file's `fp contract(off)`:
-// the toolchain's __dmul_rn / __dadd_rn are inline functions of a header compiled under its own contraction
-// setting, and a product of theirs that feeds a sum is fused into one FMA.  A member test on the ball's surface
-// must not depend on that, so the distance uses these.
-__device__ inline double mul_rn(double a, double b) { return a * b; }
-__device__ inline double add_rn(double a, double b) { return a + b; }
-
-// query_radius' reduced-distance test for the Euclidean metric, in the restatement's evaluation order
-__device__ inline bool in_ball(double x, double y, double z, double cx, double cy, double cz, double r2) {
-  const double dx = add_rn(x, -cx), dy = add_rn(y, -cy), dz = add_rn(z, -cz);
-  return add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz)) <= r2;
-}
-
-template <bool kBall>
-__device__ inline int sample_scene(const BallParams& Q, int b) {
-  if constexpr (kBall) return Q.scene_of[b];
-  else return b;
-}
-
-template <bool kBall>
-__device__ inline bool member(const float* __restrict__ xyz, int64_t i, const BallParams& Q, int b) {
-  if constexpr (kBall)
-    return in_ball((double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], Q.centre[3 * b],
-                   Q.centre[3 * b + 1], Q.centre[3 * b + 2], Q.r2);
-  else
-    return true;
-}
-
-// order-preserving map of doubles onto int64 (for atomic min / max)
-__device__ inline long long ord_of(double d) {
-  long long i = __double_as_longlong(d);
-  return i >= 0 ? i : (i ^ 0x7fffffffffffffffll);
-}
-__host__ __device__ inline double dbl_of(long long i) {
-  const long long j = i >= 0 ? i : (i ^ 0x7fffffffffffffffll);
-#ifdef __HIP_DEVICE_COMPILE__
-  return __longlong_as_double(j);
-#else
-  double d;
-  __builtin_memcpy(&d, &j, sizeof d);
-  return d;
-#endif
-}
-
-__device__ inline void transform(const float* __restrict__ xyz, int64_t i, const double* r, const double* c1,
-                                 const double* c2, double (&t)[3]) {
-  const double a0 = (double)xyz[3 * i], a1 = (double)xyz[3 * i + 1], a2 = (double)xyz[3 * i + 2];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    double v = __dadd_rn(__dadd_rn(__dmul_rn(a0, r[j]), __dmul_rn(a1, r[3 + j])), __dmul_rn(a2, r[6 + j]));
-    v = __dadd_rn(v, c1[j]);
-    t[j] = __dadd_rn(v, c2[j]);
-  }
-}
 
 template <bool kBall>
 __global__ __launch_bounds__(kMT) void merge_minmax_kernel(const float* __restrict__ xyz,
@@ -185,10 +111,18 @@ __global__ void merge_offset_kernel(const long long* __restrict__ mm, int B, dou
   offset[e] = __dadd_rn(__dadd_rn(-m, __dmul_rn(q1, P.u1[e])), __dmul_rn(q2, P.u2[e]));
 }
 
+// kElastic: the point's t was displaced by msp_merge_elastic and is read from D (row d) instead of transformed
+template <bool kElastic>
 __device__ inline bool kept(const float* __restrict__ xyz, int64_t i, int b, const MergeParams& P,
-                            const double* __restrict__ offset, double fs, double (&p)[3]) {
+                            const double* __restrict__ D, int64_t d, const double* __restrict__ offset, double fs,
+                            double (&p)[3]) {
   double t[3];
-  transform(xyz, i, P.rot + 9 * b, P.c1 + 3 * b, P.c2 + 3 * b, t);
+  if constexpr (kElastic) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) t[j] = D[3 * d + j];
+  } else {
+    transform(xyz, i, P.rot + 9 * b, P.c1 + 3 * b, P.c2 + 3 * b, t);
+  }
   bool ok = true;
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
@@ -199,10 +133,11 @@ __device__ inline bool kept(const float* __restrict__ xyz, int64_t i, int b, con
 }
 
 // counts[b * nbx + bx] = kept points of block (b, bx)
-template <bool kBall>
+template <bool kBall, bool kElastic>
 __global__ __launch_bounds__(kMT) void merge_count_kernel(const float* __restrict__ xyz,
                                                           const int64_t* __restrict__ sstart, MergeParams P,
-                                                          BallParams Q, const double* __restrict__ offset, double fs,
+                                                          BallParams Q, const double* __restrict__ D,
+                                                          const double* __restrict__ offset, double fs,
                                                           int64_t* __restrict__ counts) {
   const int b = blockIdx.y, sc = sample_scene<kBall>(Q, b);
   const int64_t s0 = sstart[sc], s1 = sstart[sc + 1];
@@ -210,7 +145,9 @@ __global__ __launch_bounds__(kMT) void merge_count_kernel(const float* __restric
   for (int k = 0; k < kMIt; ++k) {
     const int64_t i = s0 + (int64_t)blockIdx.x * kMPB + k * kMT + threadIdx.x;
     double p[3];
-    if (i < s1 && member<kBall>(xyz, i, Q, b) && kept(xyz, i, b, P, offset, fs, p)) ++c;
+    if (i < s1 && member<kBall>(xyz, i, Q, b) &&
+        kept<kElastic>(xyz, i, b, P, D, ((int64_t)b * gridDim.x) * kMPB + (i - s0), offset, fs, p))
+      ++c;
   }
   int64_t tot;
   block_excl_scan<kMT>(c, &tot);
@@ -219,12 +156,13 @@ __global__ __launch_bounds__(kMT) void merge_count_kernel(const float* __restric
 
 // stable compaction: output position = block start + prefix of the kept
 // points in point order (thread-major inside each of the kMIt sweeps)
-template <bool kBall>
+template <bool kBall, bool kElastic>
 __global__ __launch_bounds__(kMT) void merge_write_kernel(const float* __restrict__ xyz,
                                                           const float* __restrict__ rgb,
                                                           const int64_t* __restrict__ lab_in,
                                                           const int64_t* __restrict__ sstart, MergeParams P,
-                                                          BallParams Q, const double* __restrict__ offset, double fs,
+                                                          BallParams Q, const double* __restrict__ D,
+                                                          const double* __restrict__ offset, double fs,
                                                           const int64_t* __restrict__ starts,
                                                           int64_t* __restrict__ coords, float* __restrict__ feats,
                                                           int64_t* __restrict__ lab_out, int64_t* __restrict__ ids,
@@ -236,7 +174,8 @@ __global__ __launch_bounds__(kMT) void merge_write_kernel(const float* __restric
   for (int k = 0; k < kMIt; ++k) {
     const int64_t i = s0 + (int64_t)blockIdx.x * kMPB + k * kMT + threadIdx.x;
     double p[3];
-    const bool keep = i < s1 && member<kBall>(xyz, i, Q, b) && kept(xyz, i, b, P, offset, fs, p);
+    const bool keep = i < s1 && member<kBall>(xyz, i, Q, b) &&
+                      kept<kElastic>(xyz, i, b, P, D, ((int64_t)b * gridDim.x) * kMPB + (i - s0), offset, fs, p);
     int64_t tot;
     const int64_t e = pos + block_excl_scan<kMT>((int64_t)keep, &tot);
     if (keep) {
@@ -331,6 +270,61 @@ __global__ __launch_bounds__(kMT) void ball_count_kernel(const float* __restrict
   }
 }
 
+MergeWs merge_carve(void* ws, int B, int64_t max_scene_points) {
+  MergeWs W;
+  W.nbx = ceil_div(max_scene_points > 0 ? max_scene_points : 1, kMPB);
+  W.m = (int64_t)B * W.nbx;
+  char* w = static_cast<char*>(ws);
+  W.mm = reinterpret_cast<long long*>(w);
+  w += (size_t)B * 6 * sizeof(long long);
+  W.offset = reinterpret_cast<double*>(w);
+  w += (size_t)B * 3 * sizeof(double);
+  W.label_mask = reinterpret_cast<unsigned*>(w);
+  w += ((size_t)B * sizeof(unsigned) + 7) / 8 * 8;
+  W.counts = reinterpret_cast<int64_t*>(w);
+  W.starts = W.counts + W.m;
+  W.total = W.starts + W.m;
+  W.sws = W.total + 1;
+  return W;
+}
+
+void merge_begin(const MergeWs& W, int B, hipStream_t s) {
+  merge_init_kernel<<<(unsigned)ceil_div(6 * B, 256), 256, 0, s>>>(W.mm, W.label_mask, B);
+}
+
+// The passes after the per-sample min/max: offset, count, scan, stable write, finish.
+template <bool kBall, bool kElastic>
+int merge_tail(const char* what, const float* xyz, const float* rgb, const int64_t* labels,
+               const int64_t* scene_start, int B, int mode, double full_scale, MergeParams P, BallParams Q,
+               const double* D, int n_classes, int64_t* coords, float* feats, int64_t* labels_out,
+               int64_t* point_ids, int64_t point_id_base, int64_t* batch_offsets, float* scene_labels,
+               const MergeWs& W, hipStream_t s) {
+  const dim3 grid((unsigned)W.nbx, (unsigned)B);
+  merge_offset_kernel<<<(unsigned)ceil_div(3 * B, 64), 64, 0, s>>>(W.mm, B, full_scale, mode, P, W.offset);
+  merge_count_kernel<kBall, kElastic><<<grid, kMT, 0, s>>>(xyz, scene_start, P, Q, D, W.offset, full_scale, W.counts);
+  int rc = scan_exclusive_i64(W.counts, W.starts, W.m, W.total, W.sws, scan_ws_bytes(W.m), s);
+  if (rc) return rc;
+  merge_write_kernel<kBall, kElastic><<<grid, kMT, 0, s>>>(xyz, rgb, labels, scene_start, P, Q, D, W.offset,
+                                                           full_scale, W.starts, coords, feats, labels_out,
+                                                           point_ids, point_id_base, W.label_mask);
+  const int nf = (B + 1) > B * n_classes ? B + 1 : B * n_classes;
+  merge_finish_kernel<<<(unsigned)ceil_div(nf, 256), 256, 0, s>>>(W.starts, (int)W.nbx, B, W.total, W.label_mask,
+                                                                  n_classes, batch_offsets, scene_labels);
+  return check_launch(what);
+}
+
+int merge_tail_elastic(const char* what, const float* xyz, const float* rgb, const int64_t* labels,
+                       const int64_t* scene_start, int B, double full_scale, MergeParams P, BallParams Q,
+                       const double* D, int n_classes, int64_t* coords, float* feats, int64_t* labels_out,
+                       int64_t* point_ids, int64_t point_id_base, int64_t* batch_offsets, float* scene_labels,
+                       const MergeWs& W, hipStream_t s) {
+  if (Q.scene_of)
+    return merge_tail<true, true>(what, xyz, rgb, labels, scene_start, B, 0, full_scale, P, Q, D, n_classes, coords,
+                                  feats, labels_out, point_ids, point_id_base, batch_offsets, scene_labels, W, s);
+  return merge_tail<false, true>(what, xyz, rgb, labels, scene_start, B, 0, full_scale, P, Q, D, n_classes, coords,
+                                 feats, labels_out, point_ids, point_id_base, batch_offsets, scene_labels, W, s);
+}
+
 // The launches of msp_merge (kBall = false) and msp_merge_ball (kBall = true); arguments already validated.
 template <bool kBall>
 int merge_launch(const char* what, const float* xyz, const float* rgb, const int64_t* labels,
@@ -338,32 +332,12 @@ int merge_launch(const char* what, const float* xyz, const float* rgb, const int
                  MergeParams P, BallParams Q, int n_classes, int64_t* coords, float* feats, int64_t* labels_out,
                  int64_t* point_ids, int64_t point_id_base, int64_t* batch_offsets, float* scene_labels, void* ws,
                  hipStream_t s) {
-  const int64_t nbx = ceil_div(max_scene_points > 0 ? max_scene_points : 1, kMPB);
-  const int64_t m = (int64_t)B * nbx;
-  char* w = static_cast<char*>(ws);
-  long long* mm = reinterpret_cast<long long*>(w);
-  w += (size_t)B * 6 * sizeof(long long);
-  double* offset = reinterpret_cast<double*>(w);
-  w += (size_t)B * 3 * sizeof(double);
-  unsigned* label_mask = reinterpret_cast<unsigned*>(w);
-  w += ((size_t)B * sizeof(unsigned) + 7) / 8 * 8;
-  int64_t* counts = reinterpret_cast<int64_t*>(w);
-  int64_t* starts = counts + m;
-  int64_t* total = starts + m;
-  void* sws = total + 1;
-  merge_init_kernel<<<(unsigned)ceil_div(6 * B, 256), 256, 0, s>>>(mm, label_mask, B);
-  const dim3 grid((unsigned)nbx, (unsigned)B);
-  merge_minmax_kernel<kBall><<<grid, kMT, 0, s>>>(xyz, scene_start, P, Q, mm);
-  merge_offset_kernel<<<(unsigned)ceil_div(3 * B, 64), 64, 0, s>>>(mm, B, full_scale, mode, P, offset);
-  merge_count_kernel<kBall><<<grid, kMT, 0, s>>>(xyz, scene_start, P, Q, offset, full_scale, counts);
-  int rc = scan_exclusive_i64(counts, starts, m, total, sws, scan_ws_bytes(m), s);
-  if (rc) return rc;
-  merge_write_kernel<kBall><<<grid, kMT, 0, s>>>(xyz, rgb, labels, scene_start, P, Q, offset, full_scale, starts,
-                                                 coords, feats, labels_out, point_ids, point_id_base, label_mask);
-  const int nf = (B + 1) > B * n_classes ? B + 1 : B * n_classes;
-  merge_finish_kernel<<<(unsigned)ceil_div(nf, 256), 256, 0, s>>>(starts, (int)nbx, B, total, label_mask,
-                                                                  n_classes, batch_offsets, scene_labels);
-  return check_launch(what);
+  const MergeWs W = merge_carve(ws, B, max_scene_points);
+  merge_begin(W, B, s);
+  merge_minmax_kernel<kBall><<<dim3((unsigned)W.nbx, (unsigned)B), kMT, 0, s>>>(xyz, scene_start, P, Q, W.mm);
+  return merge_tail<kBall, false>(what, xyz, rgb, labels, scene_start, B, mode, full_scale, P, Q, nullptr, n_classes,
+                                  coords, feats, labels_out, point_ids, point_id_base, batch_offsets, scene_labels,
+                                  W, s);
 }
 
 }  // namespace msp

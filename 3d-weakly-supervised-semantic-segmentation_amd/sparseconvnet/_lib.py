@@ -131,6 +131,9 @@ PROTOTYPES = {
     "msp_merge_ball_workspace_size": (SZ, [I, I64]),
     "msp_merge_ball": (I, [P, P, P, P, I, I64, I, D, P, P, P, P, P, P, I, P, P, P, P, I64, P, P, P, SZ, P, P, D,
                            P]),
+    "msp_merge_elastic_workspace_size": (SZ, [I, I64, I64]),
+    "msp_merge_elastic": (I, [P, P, P, P, I, I64, I, D, P, P, P, P, P, P, I, P, P, P, P, I64, P, P, P, SZ, P, P, D,
+                              P, P, P, P, P, P, I64, I, D, I, D, P, P]),
 }
 
 _lib = None

@@ -15,6 +15,11 @@ never materialised: `SubcloudPool` draws the anchors on the host, counts
 their members on the device (`msp_ball_count`) and keeps a list of
 (scene, centre); `train_merge_subcloud_gpu` assembles a batch of such samples
 with `msp_merge_ball`, the same kernels with the ball test fused in.
+
+Elastic distortion (`elastic_deformation: True`, `dataset/data.py:171-173`; restated in `wsss3d/elastic.py`):
+`elastic=True` on the two training calls displaces every sample by two smooth random fields between the rotation
+and the offset (`msp_merge_elastic`).  The noise grids are drawn on the host at a shape bounded from the scene's
+`abs_extrema` and the rotation, so nothing is read back in the middle of a batch.
 """
 from __future__ import annotations
 
@@ -25,6 +30,7 @@ from sparseconvnet import _lib
 from sparseconvnet._lib import call, ptr
 
 from .edict import EasyDict
+from .elastic import ball_abs_extrema, sample_elastic_params
 from .subcloud import anchor_noise, anchors_from_extrema
 from .synthetic import NUM_CLASSES, train_params, val_params
 
@@ -45,9 +51,21 @@ class DeviceScenes:
         self.labels = torch.from_numpy(np.concatenate([c for _, _, c in scenes]).astype(np.int64)).to(dev)
         self.start_dev = torch.tensor(self.start, dtype=torch.int64, device=dev)
         self.device = dev
+        self._abs_extrema = None
 
     def __len__(self):
         return len(self.start) - 1
+
+    @property
+    def abs_extrema(self):
+        """Per-scene max |raw xyz| (n_scenes, 3) f64 on the host (zeros for an empty scene): the bound the elastic
+        noise grids are sized from.  Computed on the device at the first use, one read-back."""
+        if self._abs_extrema is None:
+            zero = torch.zeros(3, dtype=torch.float32, device=self.device)
+            ext = torch.stack([self.xyz[s0:s1].abs().amax(0) if s1 > s0 else zero
+                               for s0, s1 in zip(self.start[:-1], self.start[1:])])
+            self._abs_extrema = ext.cpu().numpy().astype(np.float64)
+        return self._abs_extrema
 
 
 def _param_tensors(params, dev):
@@ -84,11 +102,83 @@ def _merge(sc: DeviceScenes, params, mode, full_scale, point_id_base=0):
     return coords[:n], feats[:n], labels[:n], (ids[:n] if ids is not None else None), off, scene_labels
 
 
-def train_merge_gpu(sc: DeviceScenes, scale: float, full_scale: int = 4096, seed: int = 0):
+def _field_tensors(eparams, field, dev):
+    """Field `field`'s raw noise of every sample as msp_merge_elastic reads it: (noise f32 flat, cap (B,3) int32,
+    cell_off (B+1,) int64) on the device and the cell total."""
+    caps = np.stack([np.asarray(e["cap%d" % field], np.int64) for e in eparams])
+    off = np.concatenate([[0], np.cumsum(caps.prod(1))]).astype(np.int64)
+    flat = []
+    for e, cap in zip(eparams, caps):
+        for n in e["noise%d" % field]:
+            if n.shape != tuple(cap) or n.dtype != np.float32:
+                raise ValueError(f"elastic noise of shape {n.shape} / {n.dtype}, expected {tuple(cap)} float32")
+            flat.append(n.ravel())
+    noise = torch.from_numpy(np.concatenate(flat)).to(dev)
+    return noise, torch.from_numpy(caps.astype(np.int32)).to(dev), torch.from_numpy(off).to(dev), int(off[-1])
+
+
+def merge_elastic_gpu(sc: DeviceScenes, params, eparams, full_scale, scene_of=None, centres=None, r2=0.0,
+                      capacity=None):
+    """The lower-level call behind `elastic=True`: `trainMerge` with the draws params[b] (`train_params`' tuple)
+    and eparams[b] (`wsss3d.elastic.elastic_params`' dict) of sample b.  Sample b is scene b, or with scene_of
+    (list of int) and centres ((B,3) f64) the ball of squared radius r2 around centres[b] in scene scene_of[b].
+    All samples share eparams[0]'s gran / mag.  capacity: output rows (default: all points of the scenes).
+    Returns (coords, feats, labels, point_ids, batch_offsets list, scene_labels); raises RuntimeError when a
+    grid turned out smaller than the data needs (status != 0)."""
+    dev = sc.device
+    B = len(params)
+    if B < 1 or len(eparams) != B:
+        raise ValueError("merge_elastic_gpu: one params and one eparams entry per sample")
+    e0 = eparams[0]
+    for e in eparams:
+        if any(e[k] != e0[k] for k in ("gran1", "mag1", "gran2", "mag2")):
+            raise ValueError("merge_elastic_gpu: every sample of a batch has the same gran / mag")
+    rot, c1, c2, u1, u2, shift = _param_tensors(params, dev)
+    noise1, cap1, off1, n1 = _field_tensors(eparams, 1, dev)
+    noise2, cap2, off2, n2 = _field_tensors(eparams, 2, dev)
+    cells = max(n1, n2)
+    balls = scene_of is not None
+    if balls:
+        scene_of_t = torch.tensor(list(scene_of), dtype=torch.int32, device=dev)
+        centre_t = torch.from_numpy(np.ascontiguousarray(centres, dtype=np.float64)).to(dev)
+    elif B != len(sc):
+        raise ValueError("merge_elastic_gpu: whole scenes need one sample per scene")
+    cap = max(int(capacity) if capacity is not None else sc.start[-1], 1)
+    coords = torch.empty((cap, 4), dtype=torch.int64, device=dev)
+    feats = torch.empty((cap, 3), dtype=torch.float32, device=dev)
+    labels = torch.empty(cap, dtype=torch.int64, device=dev)
+    ids = torch.empty(cap, dtype=torch.int64, device=dev)
+    tail = torch.zeros(B + 2, dtype=torch.int64, device=dev)  # batch_offsets[B+1], then status in the low word
+    scene_labels = torch.empty((B, NUM_CLASSES), dtype=torch.float32, device=dev)
+    wsb = int(_lib.query("msp_merge_elastic_workspace_size", B, _lib.I64(sc.max_points), _lib.I64(cells)))
+    ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
+    call("msp_merge_elastic", ptr(sc.xyz), ptr(sc.rgb), ptr(sc.labels), ptr(sc.start_dev), B, sc.max_points, 0,
+         float(full_scale), ptr(rot), ptr(c1), ptr(c2), ptr(u1), ptr(u2), ptr(shift), NUM_CLASSES, ptr(coords),
+         ptr(feats), ptr(labels), ptr(ids), 0, ptr(tail), ptr(scene_labels), ptr(ws), wsb,
+         ptr(scene_of_t) if balls else None, ptr(centre_t) if balls else None, float(r2), ptr(noise1), ptr(noise2),
+         ptr(cap1), ptr(cap2), ptr(off1), ptr(off2), cells, int(e0["gran1"]), float(e0["mag1"]), int(e0["gran2"]),
+         float(e0["mag2"]), tail.data_ptr() + 8 * (B + 1), _lib.stream(dev))
+    *off, status = tail.tolist()  # the one host read: the offsets and the status word together
+    if status:
+        raise RuntimeError(f"msp_merge_elastic: status {status}: " +
+                           ("a noise grid is smaller than its sample's extent (bb clamped to cap)" if status & 1
+                            else "inconsistent cap / cell offsets"))
+    n = off[-1]
+    return coords[:n], feats[:n], labels[:n], ids[:n], off, scene_labels
+
+
+def train_merge_gpu(sc: DeviceScenes, scale: float, full_scale: int = 4096, seed: int = 0, elastic: bool = False):
     """Device `trainMerge`: EasyDict(x=EasyDict(coords, feature, batch_offsets),
     y_orig, y) like the reference's batch (`dataset/data.py:224-238`, point-cloud
-    part); bitwise equal to wsss3d.synthetic.train_merge on the same scenes."""
+    part); bitwise equal to wsss3d.synthetic.train_merge on the same scenes.
+    elastic (the config key `elastic_deformation`): the two elastic fields of `data.py:171-173` between the
+    rotation and the offset; bitwise equal to wsss3d.elastic.train_merge_elastic."""
     params = [train_params(scale, seed, i) for i in range(len(sc))]
+    if elastic:
+        ext = sc.abs_extrema
+        eparams = [sample_elastic_params(ext[i], params[i][0], scale, seed, i) for i in range(len(sc))]
+        coords, feats, labels, _, off, sl = merge_elastic_gpu(sc, params, eparams, full_scale)
+        return EasyDict(x=EasyDict(coords=coords, feature=feats, batch_offsets=off), y_orig=labels, y=sl)
     coords, feats, labels, _, off, sl = _merge(sc, params, 0, full_scale)
     return EasyDict(x=EasyDict(coords=coords, feature=feats, batch_offsets=off), y_orig=labels, y=sl)
 
@@ -156,15 +246,30 @@ class SubcloudPool:
         return self.centres_host[self.anchor_start[idx] + k]
 
 
-def train_merge_subcloud_gpu(pool: SubcloudPool, indices, scale: float, full_scale: int = 4096, seed: int = 0):
+def train_merge_subcloud_gpu(pool: SubcloudPool, indices, scale: float, full_scale: int = 4096, seed: int = 0,
+                             elastic: bool = False):
     """Device `trainMerge` for the balls pool.entries[i], i in indices: the EasyDict of `train_merge_gpu` plus
     point_ids (each row's index into the pool's concatenated scenes); bitwise equal to
-    wsss3d.subcloud.train_merge_subcloud on the same (scene, centre) entries."""
+    wsss3d.subcloud.train_merge_subcloud on the same (scene, centre) entries.
+    elastic (`elastic_deformation`): as in `train_merge_gpu`, the grids sized from min(scene extrema, |centre| +
+    in_radius); bitwise equal to wsss3d.elastic.train_merge_subcloud_elastic."""
     sc, dev = pool.scenes, pool.scenes.device
     indices = list(indices)
     B = len(indices)
     if B < 1:
         raise ValueError("train_merge_subcloud_gpu: empty batch")
+    if elastic:
+        params = [train_params(scale, seed, b) for b in range(B)]
+        scene_of = [pool.entries[i][0] for i in indices]
+        centres = np.stack([pool.centre(i) for i in indices])
+        ext = sc.abs_extrema
+        eparams = [sample_elastic_params(ball_abs_extrema(ext[scene_of[b]], centres[b], pool.in_radius),
+                                         params[b][0], scale, seed, b) for b in range(B)]
+        coords, feats, labels, ids, off, sl = merge_elastic_gpu(
+            sc, params, eparams, full_scale, scene_of, centres, pool.r2,
+            capacity=sum(pool.entries[i][2] for i in indices))
+        return EasyDict(x=EasyDict(coords=coords, feature=feats, batch_offsets=off), y_orig=labels, y=sl,
+                        point_ids=ids)
     rot, c1, c2, u1, u2, shift = _param_tensors([train_params(scale, seed, b) for b in range(B)], dev)
     scene_of = torch.tensor([pool.entries[i][0] for i in indices], dtype=torch.int32, device=dev)
     centre = torch.from_numpy(np.stack([pool.centre(i) for i in indices])).to(dev)

@@ -584,6 +584,32 @@ int msp_merge_ball(const float* xyz, const float* rgb, const int64_t* labels, co
                    int64_t* batch_offsets, float* scene_labels, void* ws, size_t ws_bytes, const int* scene_of,
                    const double* centre, double r2, msp_stream_t stream);
 
+/* Elastic distortion in the batch assembly (`elastic_deformation: True`, dataset/data.py:171-173, additive in ABI
+ * 10): msp_merge (mode 0 only) with two smooth random displacement fields applied between the rotation and the
+ * random offset, t1 = t + g1(t) * mag1, t2 = t1 + g2(t1) * mag2, bitwise as wsss3d/elastic.py states them (fp64,
+ * every product and sum rounded separately).  Takes msp_merge_ball's arguments; scene_of and centre both NULL
+ * mean whole scenes (sample b = scene b, r2 ignored).  Field f of sample b: three grids of raw Gaussian noise (f32,
+ * drawn by the host) of shape cap_f[b][0..2] (int32, C order, each >= 2), component c at noise_f + 3 *
+ * cell_off_f[b] + c * cap0*cap1*cap2; cell_off_f[B+1] (int64) ascending with cell_off_f[b+1] - cell_off_f[b] >=
+ * cap0*cap1*cap2 and cell_off_f[B] <= cap_cells_total (all device arrays).  Per axis the field uses the first
+ * bb = int32(max |x|) / gran + 3 nodes (computed on the device from the sample's points, spacing 2 * gran), blurred
+ * six times with a 3-tap box that reads zero at and beyond bb; the caller sizes cap >= bb from a bound on the data
+ * (wsss3d/elastic.py: elastic_caps).  *status (device int, zeroed inside): bit 0 = some bb exceeded its cap and was
+ * clamped, bit 1 = a sample's cap / cell offsets are inconsistent and its fields were skipped; no index leaves the
+ * buffers in either case, but the batch is then not the specification's.  Rejected before any HIP call: NULL
+ * pointers, gran < 1, non-finite mag, B outside [1, 65535], mode != 0, n_classes > 32, one of scene_of / centre
+ * NULL, ws_bytes < msp_merge_elastic_workspace_size(B, max_scene_points, cap_cells_total). */
+size_t msp_merge_elastic_workspace_size(int B, int64_t max_scene_points, int64_t cap_cells_total);
+int msp_merge_elastic(const float* xyz, const float* rgb, const int64_t* labels, const int64_t* scene_start, int B,
+                      int64_t max_scene_points, int mode, double full_scale, const double* rot, const double* c1,
+                      const double* c2, const double* u1, const double* u2, const float* shift, int n_classes,
+                      int64_t* coords, float* feats, int64_t* labels_out, int64_t* point_ids,
+                      int64_t point_id_base, int64_t* batch_offsets, float* scene_labels, void* ws, size_t ws_bytes,
+                      const int* scene_of, const double* centre, double r2, const float* noise1,
+                      const float* noise2, const int* cap1, const int* cap2, const int64_t* cell_off1,
+                      const int64_t* cell_off2, int64_t cap_cells_total, int gran1, double mag1, int gran2,
+                      double mag2, int* status, msp_stream_t stream);
+
 /* The training step's optimizer (round 6, ABI 10): torch.optim.Adam (the reference's train.py:39, Adam(lr=1e-3);
  * amsgrad off) over up to MSP_ADAM_MAX_TENSORS parameter tensors in one launch.  table: device array of n
  * msp_adam_tensor (param, exp_avg, exp_avg_sq: fp32, n floats each, contiguous); chunk_start: device exclusive
