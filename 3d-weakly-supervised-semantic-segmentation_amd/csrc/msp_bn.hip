@@ -768,7 +768,11 @@ int msp_add_bn_stats(const float* a, const float* b, int64_t V, int C, float* su
   } else {
     const int64_t n = V * C;
     if (n > 0) add_kernel<<<ew_grid(n), kT, 0, s>>>(a, b, n, sum);
-    bn_reduce_kernel<0><<<(unsigned)bn_parts(V, C), kT, 0, s>>>(sum, nullptr, V, C, nullptr, 0.f, partial);
+    // the form msp_bn_stats takes on sum (an unaligned a or b lands here with sum aligned): identical partials
+    if (C % 4 == 0 && C <= 4 * kT && aligned16(sum))
+      bn_reduce4_kernel<0><<<(unsigned)bn_parts(V, C), kT, 0, s>>>(sum, nullptr, V, C, nullptr, 0.f, partial);
+    else
+      bn_reduce_kernel<0><<<(unsigned)bn_parts(V, C), kT, 0, s>>>(sum, nullptr, V, C, nullptr, 0.f, partial);
   }
   return check_launch("msp_add_bn_stats");
 }

@@ -741,8 +741,10 @@ def test_join_bn_split_backward_matches_split_pass(ca, cb, residual, monkeypatch
     BN-SubM-BN-SubM) + AddTable; else BN -> SubM): with ops.FUSE_JOIN_SPLIT the BN's backward writes the join
     inputs' gradients as two blocks (msp_bn_bwd_apply_split, ops.BatchNormJoinFunction) instead of a [V][C] dx
     that msp_split_cols then splits.  Outputs, both inputs' gradients, every parameter gradient and the running
-    statistics are bit-identical to the split pass (the same arithmetic per element); 6 + 10 channels take the
-    scalar kernel.  A second consumer of the joined tensor still gets its gradient through the join."""
+    statistics are bit-identical to the split pass (the same arithmetic per element).  The 6 + 10 join takes the
+    copy kernel (neither width is a multiple of 4) and its C = 16 BN backward the vector split kernel with element
+    stores; the scalar split kernel is covered by tests/test_gpu_bn.py.  A second consumer of the joined tensor
+    still gets its gradient through the join."""
     from sparseconvnet import ops
     monkeypatch.setattr(ops, "FUSE_BN_STATS", False)
     torch.manual_seed(ca + 7 * cb)
