@@ -6,8 +6,11 @@
 //   msp_confusion       iou.confusion_matrix on device label vectors
 //   msp_point_ce_*      cross entropy over the rows whose label is not -100, without the boolean gather:
 //                       the kept count stays on the device, so the step can be captured into a graph
+//   msp_voxel_ce_*      the same loss, and the adjoint of the scene mean of the logits, on the level-0 voxel rows:
+//                       all points of a voxel share one logit row, so the log-sum-exp is taken once per voxel and
+//                       a voxel's gradient row is (kept_v softmax_v - hist_v) / n_kept; no (N, C) tensor is formed
 //
-// All three stream (N, C) f32 rows with C <= 64.  A tile of R = blockDim.x rows is contiguous in memory
+// The first three stream (N, C) f32 rows with C <= 64.  A tile of R = blockDim.x rows is contiguous in memory
 // (R * C floats), so a block loads it with 16-byte loads in memory order and scatters it into an LDS image
 // with an odd row stride; after the barrier lane t owns row t and walks its C columns conflict-free (odd
 // stride: the 32 lanes of a half-wave sit on 32 different banks).  The CE backward writes its gradient tile
@@ -22,6 +25,7 @@ namespace msp {
 constexpr int kMaxC = 64;          // classes (the reference has 20)
 constexpr int kCePartials = 1024;  // stage-1 blocks of the CE loss sum (fixed: the sum's order is part of the result)
 constexpr int kIgnore = -100;
+constexpr int kMaxLd = 1024;      // row stride of the voxel rows: tile elements e * ld < 2^32 keep div_c exact
 
 inline int tile_rows(int C) { return C <= 48 ? 256 : 128; }  // R * (C | 1) * 4 B  <=  50 KiB of LDS per block
 inline int lds_stride(int C) { return C | 1; }
@@ -322,6 +326,250 @@ __global__ __launch_bounds__(256) void point_ce_bwd_kernel(const float* __restri
   }
 }
 
+// ---------------------------------------------------------------- cross entropy on the voxel rows
+// A tile is R = blockDim.x voxel rows of row stride ld >= C; z = row[:C] + bias is staged into the same LDS image
+// as above (memory-order loads of the whole padded rows, columns >= C dropped), lane t owns voxel row0 + t: it
+// takes the row's lse and walks the voxel's points perm[vstart[v] .. vstart[v+1]).  Neighbouring lanes walk
+// neighbouring runs of perm, so those reads coalesce; the labels are an 8-byte gather in point order.  A voxel
+// with more than kHeavyPoints points is not walked by its lane: the wave takes such voxels one after the other,
+// 64 points per step, so a crowded voxel costs cnt / 64 dependent gathers instead of cnt.
+constexpr int kHeavyPoints = 64;
+
+__device__ inline void stage_voxel_tile(const float* __restrict__ vl, int64_t row0, int nr, int ld, int C, int S,
+                                        uint32_t magic_ld, bool vec, const float* __restrict__ bias,
+                                        float* __restrict__ tile) {
+  const float* p = vl + row0 * ld;
+  const uint32_t nflt = (uint32_t)nr * (uint32_t)ld;
+  const uint32_t n4 = vec ? (nflt >> 2) : 0u;  // vec: ld % 4 == 0, so a float4 never straddles two rows
+  for (uint32_t q = threadIdx.x; q < n4; q += blockDim.x) {
+    const float4 x = reinterpret_cast<const float4*>(p)[q];
+    const float xs[4] = {x.x, x.y, x.z, x.w};
+    const uint32_t r = div_c(4u * q, magic_ld);
+    const uint32_t c = 4u * q - r * (uint32_t)ld;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (c + k < (uint32_t)C) tile[r * S + c + k] = bias ? xs[k] + bias[c + k] : xs[k];
+  }
+  for (uint32_t e = 4u * n4 + threadIdx.x; e < nflt; e += blockDim.x) {
+    const uint32_t r = div_c(e, magic_ld);
+    const uint32_t c = e - r * (uint32_t)ld;
+    if (c < (uint32_t)C) tile[r * S + c] = bias ? p[e] + bias[c] : p[e];
+  }
+}
+
+// label of the j-th point of the sorted order; anything that cannot be read is ignored
+__device__ inline int64_t point_label(const int32_t* __restrict__ perm, const int64_t* __restrict__ labels,
+                                      int64_t N, int64_t j) {
+  const int64_t p = perm[j];
+  return (p >= 0 && p < N) ? labels[p] : (int64_t)kIgnore;
+}
+
+// point run of voxel v, clamped to [0, N]
+__device__ inline void point_run(const int32_t* __restrict__ vstart, int64_t v, int64_t N, int64_t& s, int64_t& e) {
+  s = vstart[v];
+  e = vstart[v + 1];
+  s = s < 0 ? 0 : (s > N ? N : s);
+  e = e < s ? s : (e > N ? N : e);
+}
+
+__device__ inline int wave_sum_int(int v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+// stage 1: block p takes tiles p, p + P, ... in order; writes lse and the kept count per voxel and its partial
+__global__ __launch_bounds__(256) void voxel_ce_fwd_kernel(const float* __restrict__ vl, int64_t V, int ld, int C,
+                                                           uint32_t magic_ld, int vec,
+                                                           const float* __restrict__ bias,
+                                                           const int32_t* __restrict__ perm,
+                                                           const int32_t* __restrict__ vstart,
+                                                           const int64_t* __restrict__ labels, int64_t N,
+                                                           float* __restrict__ lse_out, int32_t* __restrict__ kept_out,
+                                                           CePartial* __restrict__ partial) {
+  extern __shared__ float smem[];
+  __shared__ double red[4];
+  __shared__ int cnt[2];
+  const int R = blockDim.x, S = C | 1, t = threadIdx.x, lane = t & 63;
+  float* tile = smem;
+  if (t < 2) cnt[t] = 0;
+  double acc = 0.0;  // thread 0: the block's running sum
+  int64_t kept = 0, bad = 0;
+  const int64_t n_tiles = (V + R - 1) / R;
+  for (int64_t tl = blockIdx.x; tl < n_tiles; tl += gridDim.x) {
+    const int64_t row0 = tl * R;
+    const int nr = (int)(V - row0 < R ? V - row0 : R);
+    __syncthreads();
+    stage_voxel_tile(vl, row0, nr, ld, C, S, magic_ld, vec != 0, bias, tile);
+    __syncthreads();
+    double term = 0.0;
+    int nk = 0, nb = 0;
+    int64_t s = 0, e = 0;
+    float lse = 0.f;
+    bool heavy = false;
+    if (t < nr) {
+      const float* x = tile + t * S;
+      float mx = x[0];
+      for (int c = 1; c < C; ++c) mx = fmaxf(mx, x[c]);
+      float se = 0.f;
+      for (int c = 0; c < C; ++c) se += expf(x[c] - mx);
+      lse = mx + logf(se);
+      lse_out[row0 + t] = lse;
+      point_run(vstart, row0 + t, N, s, e);
+      heavy = e - s > kHeavyPoints;
+      if (!heavy) {
+        for (int64_t j = s; j < e; ++j) {
+          const int64_t y = point_label(perm, labels, N, j);
+          if (y >= 0 && y < C) {  // never index with anything else
+            term += (double)(lse - x[(int)y]);
+            ++nk;
+          } else if (y != kIgnore) {
+            ++nb;
+          }
+        }
+      }
+    }
+    for (unsigned long long hm = ballot64(heavy); hm; hm &= hm - 1) {  // wave-uniform
+      const int src = __builtin_ctzll(hm);
+      const int64_t hs = __shfl(s, src, 64), he = __shfl(e, src, 64);
+      const float hl = __shfl(lse, src, 64);
+      const float* x = tile + (t - lane + src) * S;
+      double part = 0.0;
+      int pk = 0, pb = 0;
+      for (int64_t j = hs + lane; j < he; j += 64) {
+        const int64_t y = point_label(perm, labels, N, j);
+        if (y >= 0 && y < C) {
+          part += (double)(hl - x[(int)y]);
+          ++pk;
+        } else if (y != kIgnore) {
+          ++pb;
+        }
+      }
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);  // the same tree on every run
+      pk = wave_sum_int(pk);
+      pb = wave_sum_int(pb);
+      if (lane == src) {
+        term = part;
+        nk = pk;
+        nb = pb;
+      }
+    }
+    if (t < nr) kept_out[row0 + t] = nk;
+    const int wk = wave_sum_int(nk), wb = wave_sum_int(nb);
+    if (lane == 0) {
+      if (wk) atomicAdd(&cnt[0], wk);
+      if (wb) atomicAdd(&cnt[1], wb);
+    }
+    const double sum = block_sum_fixed(term, red);  // its barriers also order cnt[]
+    if (t == 0) {
+      acc += sum;
+      kept += cnt[0];
+      bad += cnt[1];
+      cnt[0] = cnt[1] = 0;
+    }
+  }
+  if (t == 0) partial[blockIdx.x] = CePartial{acc, kept, bad};
+}
+
+// dynamic LDS: [R * S] f32 tile, [R] f32 scene weights cnt_v / n_b, [R] int scene of the row
+__global__ __launch_bounds__(256) void voxel_ce_bwd_kernel(
+    const float* vl, int64_t V, int ld, int C, uint32_t magic_ld, int vec_in, int vec_out,  // dvl may be vl
+    const float* __restrict__ bias, const int32_t* __restrict__ perm, const int32_t* __restrict__ vstart,
+    const int64_t* __restrict__ labels, int64_t N, const float* __restrict__ lse, const int32_t* __restrict__ kept,
+    const int64_t* __restrict__ n_kept, const float* __restrict__ gout, const float* __restrict__ gscene,
+    const uint64_t* __restrict__ keys, int shift, int B, const int64_t* __restrict__ npts, float* dvl) {
+  extern __shared__ float smem[];
+  const int R = blockDim.x, S = C | 1, t = threadIdx.x, lane = t & 63;
+  float* tile = smem;
+  float* rw = smem + R * S;
+  int* rb = reinterpret_cast<int*>(rw + R);
+  const int64_t nk = *n_kept;
+  const float scale = nk > 0 ? *gout / (float)nk : 0.f;  // no kept point: the CE term is zero, not NaN
+  const int64_t n_tiles = (V + R - 1) / R;
+  for (int64_t tl = blockIdx.x; tl < n_tiles; tl += gridDim.x) {
+    const int64_t row0 = tl * R;
+    const int nr = (int)(V - row0 < R ? V - row0 : R);
+    __syncthreads();
+    stage_voxel_tile(vl, row0, nr, ld, C, S, magic_ld, vec_in != 0, bias, tile);
+    __syncthreads();
+    int64_t s = 0, e = 0;
+    bool heavy = false;
+    if (t < nr) {
+      float* x = tile + t * S;
+      const int64_t v = row0 + t;
+      const int k = nk > 0 ? kept[v] : 0;
+      point_run(vstart, v, N, s, e);
+      float w = 0.f;
+      int b = 0;
+      if (gscene) {
+        const uint64_t kb = keys[v] >> shift;
+        if (kb < (uint64_t)B) {
+          b = (int)kb;
+          const int64_t n = npts[b];
+          w = n > 0 ? (float)(vstart[v + 1] - vstart[v]) / (float)n : 0.f;
+        }
+      }
+      rw[t] = w;
+      rb[t] = b;
+      if (k > 0) {
+        // kept_v softmax_v - hist_v, unscaled: the histogram is subtracted one point at a time (each step is
+        // exact until the value passes -kept_v softmax_v, and rounds to a coarser grid at most once per binade)
+        const float l = lse[v], fk = (float)k;
+        for (int c = 0; c < C; ++c) x[c] = fk * expf(x[c] - l);
+        heavy = e - s > kHeavyPoints;
+        if (!heavy) {
+          for (int64_t j = s; j < e; ++j) {
+            const int64_t y = point_label(perm, labels, N, j);
+            if (y >= 0 && y < C) x[(int)y] -= 1.f;
+          }
+        }
+      } else {
+        for (int c = 0; c < C; ++c) x[c] = 0.f;
+      }
+    }
+    for (unsigned long long hm = ballot64(heavy); hm; hm &= hm - 1) {  // wave-uniform; lane c counts class c
+      const int src = __builtin_ctzll(hm);
+      const int64_t hs = __shfl(s, src, 64), he = __shfl(e, src, 64);
+      int h = 0;
+      for (int64_t j0 = hs; j0 < he; j0 += 64) {
+        const int64_t j = j0 + lane;
+        const int64_t y = j < he ? point_label(perm, labels, N, j) : (int64_t)kIgnore;
+        const int yy = (y >= 0 && y < C) ? (int)y : -1;
+        for (int c = 0; c < C; ++c) {
+          const int n = __popcll(ballot64(yy == c));
+          if (lane == c) h += n;
+        }
+      }
+      if (lane < C) tile[(t - lane + src) * S + lane] -= (float)h;
+    }
+    __syncthreads();
+    // rows [row0, row0 + nr) of dvl in memory order: scale * tile + w * gscene[b], columns C .. ld-1 zero
+    float* p = dvl + row0 * ld;
+    const uint32_t nflt = (uint32_t)nr * (uint32_t)ld;
+    const uint32_t n4 = vec_out ? (nflt >> 2) : 0u;
+    for (uint32_t q = t; q < n4; q += R) {
+      const uint32_t r = div_c(4u * q, magic_ld);
+      const uint32_t c = 4u * q - r * (uint32_t)ld;
+      const float w = rw[r];
+      const float* g = gscene ? gscene + (int64_t)rb[r] * C : nullptr;
+      float xs[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t ck = c + k;
+        xs[k] = ck < (uint32_t)C ? scale * tile[r * S + ck] + (g ? w * g[ck] : 0.f) : 0.f;
+      }
+      reinterpret_cast<float4*>(p)[q] = make_float4(xs[0], xs[1], xs[2], xs[3]);
+    }
+    for (uint32_t el = 4u * n4 + t; el < nflt; el += R) {
+      const uint32_t r = div_c(el, magic_ld);
+      const uint32_t c = el - r * (uint32_t)ld;
+      p[el] = c < (uint32_t)C ? scale * tile[r * S + c] + (gscene ? rw[r] * gscene[(int64_t)rb[r] * C + c] : 0.f)
+                              : 0.f;
+    }
+  }
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline size_t tile_lds(int C) { return (size_t)tile_rows(C) * lds_stride(C) * sizeof(float); }
 inline int ce_partials(int64_t N, int C) {
@@ -396,6 +644,50 @@ int msp_point_ce_bwd(const float* logits, int64_t N, int C, const int64_t* label
       logits, N, C, div_magic(C), aligned16(logits) ? 1 : 0, aligned16(dlogits) ? 1 : 0, labels, lse, n_kept, gout,
       dlogits);
   return check_launch("msp_point_ce_bwd");
+}
+
+size_t msp_voxel_ce_workspace_size(int64_t V) { return msp_point_ce_workspace_size(V); }
+
+int msp_voxel_ce_fwd(const float* vl, int64_t V, int64_t ld, int C, const float* bias, const int32_t* perm,
+                     const int32_t* vstart, const int64_t* labels, int64_t N, float* loss, int64_t* n_kept,
+                     int64_t* n_bad, float* lse, int32_t* kept, void* ws, size_t ws_bytes, msp_stream_t stream) {
+  MSP_REQUIRE(C >= 1 && C <= kMaxC, "msp_voxel_ce_fwd: C=%d outside [1, %d]", C, kMaxC);
+  MSP_REQUIRE(V >= 0 && N >= 0 && N < (1ll << 31) && ld >= C && ld <= kMaxLd,
+              "msp_voxel_ce_fwd: bad arguments (V=%lld N=%lld ld=%lld)", (long long)V, (long long)N, (long long)ld);
+  const size_t need = msp_voxel_ce_workspace_size(V);
+  MSP_REQUIRE(ws_bytes >= need, "msp_voxel_ce_fwd: workspace too small (%zu < %zu)", ws_bytes, need);
+  MSP_REQUIRE(loss && n_kept && n_bad && ws, "msp_voxel_ce_fwd: NULL pointer");
+  MSP_REQUIRE(V == 0 || (vl && perm && vstart && labels && lse && kept), "msp_voxel_ce_fwd: NULL pointer");
+  hipStream_t s = as_stream(stream);
+  CePartial* partial = static_cast<CePartial*>(ws);
+  const int P = ce_partials(V, C);
+  if (P > 0)
+    voxel_ce_fwd_kernel<<<P, tile_rows(C), tile_lds(C), s>>>(vl, V, (int)ld, C, div_magic((int)ld),
+                                                             (aligned16(vl) && ld % 4 == 0) ? 1 : 0, bias, perm,
+                                                             vstart, labels, N, lse, kept, partial);
+  point_ce_final_kernel<<<1, 256, 0, s>>>(partial, P, loss, n_kept, n_bad);
+  return check_launch("msp_voxel_ce_fwd");
+}
+
+int msp_voxel_ce_bwd(const float* vl, int64_t V, int64_t ld, int C, const float* bias, const int32_t* perm,
+                     const int32_t* vstart, const int64_t* labels, int64_t N, const float* lse, const int32_t* kept,
+                     const int64_t* n_kept, const float* gout, const float* gscene, const uint64_t* keys, int shift,
+                     int B, const int64_t* npts, float* dvl, msp_stream_t stream) {
+  MSP_REQUIRE(C >= 1 && C <= kMaxC, "msp_voxel_ce_bwd: C=%d outside [1, %d]", C, kMaxC);
+  MSP_REQUIRE(V >= 0 && N >= 0 && N < (1ll << 31) && ld >= C && ld <= kMaxLd,
+              "msp_voxel_ce_bwd: bad arguments (V=%lld N=%lld ld=%lld)", (long long)V, (long long)N, (long long)ld);
+  if (V == 0) return MSP_OK;
+  MSP_REQUIRE(vl && perm && vstart && labels && lse && kept && n_kept && gout && dvl,
+              "msp_voxel_ce_bwd: NULL pointer");
+  MSP_REQUIRE(!gscene || (keys && npts && B >= 1 && shift >= 0 && shift < 64),
+              "msp_voxel_ce_bwd: the scene term needs keys, npts, B >= 1 and a shift in [0, 64)");
+  const int R = tile_rows(C);
+  const size_t lds = tile_lds(C) + (size_t)R * (sizeof(float) + sizeof(int));
+  voxel_ce_bwd_kernel<<<stream_grid(ceil_div(V, R), lds), R, lds, as_stream(stream)>>>(
+      vl, V, (int)ld, C, div_magic((int)ld), (aligned16(vl) && ld % 4 == 0) ? 1 : 0,
+      (aligned16(dvl) && ld % 4 == 0) ? 1 : 0, bias, perm, vstart, labels, N, lse, kept, n_kept, gout, gscene, keys,
+      shift, B, npts, dvl);
+  return check_launch("msp_voxel_ce_bwd");
 }
 
 }  // extern "C"

@@ -125,6 +125,9 @@ PROTOTYPES = {
     "msp_point_ce_workspace_size": (SZ, [I64]),
     "msp_point_ce_fwd": (I, [P, I64, I, P, P, P, P, P, P, SZ, P]),
     "msp_point_ce_bwd": (I, [P, I64, I, P, P, P, P, P, P]),
+    "msp_voxel_ce_workspace_size": (SZ, [I64]),
+    "msp_voxel_ce_fwd": (I, [P, I64, I64, I, P, P, P, P, I64, P, P, P, P, P, P, SZ, P]),
+    "msp_voxel_ce_bwd": (I, [P, I64, I64, I, P, P, P, P, I64, P, P, P, P, P, P, I, I, P, P, P]),
     "msp_merge_workspace_size": (SZ, [I, I64]),
     "msp_merge": (I, [P, P, P, P, I, I64, I, D, P, P, P, P, P, P, I, P, P, P, P, I64, P, P, P, SZ, P]),
     "msp_ball_count": (I, [P, P, I, I64, P, P, D, P, P]),

@@ -1175,6 +1175,82 @@ class PointCrossEntropyFunction(torch.autograd.Function):
         return dlogits, None
 
 
+class VoxelCrossEntropyFunction(torch.autograd.Function):
+    """The pseudo-label training tail (models/MultiLabelContrastive.py:88-94 with utils/loss.py:29-33) on the
+    level-0 voxel rows: with logits[p] = W x[v(p)] + b, returns (scene_logits (B, C) = per-scene means of the
+    per-point logits, F.cross_entropy over the points whose label is not -100, n_kept, n_bad) without the (N, C)
+    logits or their gradient.  Forward: the Linear on the voxel rows (msp_nin_gemm), msp_voxel_ce_fwd (one lse per
+    voxel), msp_scene_mean_fwd on the padded rows.  Backward: one msp_voxel_ce_bwd writes the voxel rows' gradient
+    (CE term in closed form + the scene mean's adjoint) over the saved rows, then dx / dW / db as
+    PointLogitsFunction.  No host read in either direction.  The rows are overwritten by their gradient, so a
+    second backward through the same forward raises, as torch does once it has freed a graph's buffers."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, labels, level, rules, B):
+        _check_feats(x)
+        x = x.contiguous()
+        V, C = x.shape
+        n_out = weight.size(0)
+        if weight.size(1) != C:
+            raise ValueError(f"VoxelCrossEntropy: Linear({weight.size(1)}, {n_out}) on {C} channels")
+        if n_out > PSEUDO_MAX_CLASSES:
+            raise ValueError(f"VoxelCrossEntropy: {n_out} classes, at most {PSEUDO_MAX_CLASSES}")
+        N = rules.n_points
+        labels = _check_labels(labels, N, "VoxelCrossEntropy: labels")
+        dev = x.device
+        bias = bias.contiguous() if bias is not None else None
+        vl = nin_gemm(x, weight.t(), kind="logits_fwd", keep_pad=True)  # (V, pad16(n_out))
+        ld = vl.size(1)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        nums = torch.empty(2, dtype=torch.int64, device=dev)
+        lse = torch.empty(max(V, 1), dtype=torch.float32, device=dev)
+        kept = torch.empty(max(V, 1), dtype=torch.int32, device=dev)
+        wsb = int(_lib.query("msp_voxel_ce_workspace_size", V))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        call("msp_voxel_ce_fwd", ptr(vl), V, ld, n_out, ptr(bias), ptr(rules.perm), ptr(rules.vstart), ptr(labels), N,
+             ptr(loss), ptr(nums), ptr(nums[1:]), ptr(lse), ptr(kept), ptr(ws), wsb, _stream(x))
+        vscene = torch.empty(B + 1, dtype=torch.int64, device=dev)
+        npts = torch.empty(B, dtype=torch.int64, device=dev)
+        means = torch.empty((B, ld), dtype=torch.float32, device=dev)
+        shift = 3 * level.log2
+        wsb = int(_lib.query("msp_scene_mean_workspace_size", V, B, ld))
+        ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
+        call("msp_scene_mean_fwd", ptr(vl), ld, ptr(level.keys), V, shift, ptr(rules.vstart), B, ptr(vscene),
+             ptr(npts), ptr(means), ptr(ws), wsb, _stream(x))
+        # a scene without points has the mean 0 (msp_scene_mean_fwd) and, as in backward, no bias either
+        scene = means[:, :n_out].contiguous() if bias is None else means[:, :n_out] + bias * (npts > 0)[:, None]
+        ctx.save_for_backward(x, weight, bias, labels, vl, lse, kept, nums, npts)
+        ctx.level, ctx.rules, ctx.shift, ctx.B, ctx.spent = level, rules, shift, B, False
+        n_kept, n_bad = nums[0], nums[1]
+        ctx.mark_non_differentiable(n_kept, n_bad)
+        return scene, loss, n_kept, n_bad
+
+    @staticmethod
+    def backward(ctx, gscene, g, _gk, _gb):
+        x, weight, bias, labels, vl, lse, kept, nums, npts = ctx.saved_tensors
+        if ctx.spent:
+            raise RuntimeError("VoxelCrossEntropy: backward a second time through one forward (the saved voxel "
+                               "logits now hold their gradient); run the forward again")
+        ctx.spent = True
+        V, ld = vl.shape
+        n_out = weight.size(0)
+        rules = ctx.rules
+        g = g.to(torch.float32).contiguous()
+        gscene = gscene.to(torch.float32).contiguous()
+        call("msp_voxel_ce_bwd", ptr(vl), V, ld, n_out, ptr(bias), ptr(rules.perm), ptr(rules.vstart), ptr(labels),
+             rules.n_points, ptr(lse), ptr(kept), ptr(nums), ptr(g), ptr(gscene), ptr(ctx.level.keys), ctx.shift,
+             ctx.B, ptr(npts), ptr(vl), _stream(vl))
+        dvl = vl  # (V, ld), columns n_out.. zero
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = nin_gemm(dvl, F.pad(weight, (0, 0, 0, ld - n_out)), kind="logits_bwd_data")
+        if ctx.needs_input_grad[1]:
+            dw = _site_wgrad(x, dvl, "logits_wgrad")[:, :n_out].t()
+        if bias is not None and ctx.needs_input_grad[2]:
+            db = dvl.sum(0)[:n_out]
+        return dx, dw, db, None, None, None, None
+
+
 class UnPoolingFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, rules, n_fine):

@@ -12,10 +12,10 @@ from . import encoders, evaluate, heads, pseudo, text, tokenizer  # noqa: F401  
 from .encoders import SparseConvBase_, segment_mean
 from .merge import DeviceScenes, SubcloudPool, train_merge_gpu, train_merge_subcloud_gpu, val_merge_gpu
 from .pseudo import (PseudoLabelPass, assess_label_quality, get_pseudo_labels, point_cross_entropy,
-                     store_pseudo_label)
+                     store_pseudo_label, voxel_point_cross_entropy)
 from .tokenizer import text_transform
 
 __all__ = ["EasyDict", "Registry", "MODEL_REGISTRY", "LOSS_REGISTRY", "SparseConvBase_", "segment_mean",
            "text_transform", "PseudoLabelPass", "assess_label_quality", "get_pseudo_labels", "point_cross_entropy",
-           "store_pseudo_label", "DeviceScenes", "SubcloudPool", "train_merge_gpu", "train_merge_subcloud_gpu",
+           "voxel_point_cross_entropy", "store_pseudo_label", "DeviceScenes", "SubcloudPool", "train_merge_gpu", "train_merge_subcloud_gpu",
            "val_merge_gpu"]

@@ -18,6 +18,7 @@ from torch import nn
 import sparseconvnet as scn
 from sparseconvnet.ops import PointLogitsFunction, SceneMeanFunction
 
+from .pseudo import point_cross_entropy, voxel_point_cross_entropy
 from .registry import MODEL_REGISTRY
 
 
@@ -78,6 +79,31 @@ class SparseConvBase_(nn.Module):
             return linear(self.encode([coords, feats]))
         t = self.encoder[:-1]([coords, feats])
         return PointLogitsFunction.apply(t.features, linear.weight, linear.bias, t.metadata.input)
+
+    def point_loss(self, x, linear: nn.Linear, labels, return_counts=False):
+        """The pseudo-label training tail (train.py:67-74 with `label: pseudo`; models/MultiLabelContrastive.py:88-94,
+        utils/loss.py:29-33): with logits = `linear(self(x))`, returns (per-scene mean logits (B, C),
+        cross entropy of the logits over the points whose label is not -100), and with return_counts also
+        (n_kept, n_bad).  Under the conditions of the fused scene means (`_fusable`, scene b = the points of
+        batch id b) both come from the level-0 voxel rows (pseudo.voxel_point_cross_entropy): neither the (N, C)
+        logits nor their gradient is formed.  Otherwise the per-point path runs: point_logits + segment_mean +
+        point_cross_entropy."""
+        off = x["batch_offsets"]
+        if self._fusable():
+            coords, feats = self._inputs(x)
+            t = self.encoder[:-1]([coords, feats])
+            rules = t.metadata.input
+            if rules.scene_ranges_match(off):
+                lvl = t.metadata.level(int(t.spatial_size[0]))
+                out = voxel_point_cross_entropy(t.features, linear.weight, linear.bias, labels, lvl, rules,
+                                                len(off) - 1, return_counts=True)
+                return out if return_counts else out[:2]
+            logits = PointLogitsFunction.apply(t.features, linear.weight, linear.bias, rules)
+        else:
+            logits = self.point_logits(x, linear)
+        scene = segment_mean(logits, off)
+        loss, n_kept, n_bad = point_cross_entropy(logits, labels, return_counts=True)
+        return (scene, loss, n_kept, n_bad) if return_counts else (scene, loss)
 
     # ---------------------------------------------------------------- fused tail
     def _fusable(self):

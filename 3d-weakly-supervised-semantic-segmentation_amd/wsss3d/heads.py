@@ -17,6 +17,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .encoders import segment_mean
+from .pseudo import point_cross_entropy
 from .registry import LOSS_REGISTRY, MODEL_REGISTRY
 from .synthetic import NUM_CLASSES
 
@@ -64,6 +65,19 @@ class FullySupervised(nn.Module):
             logits = point_logits(self.pc_encoder, pc_input, self.linear)
             return segment_mean(logits, pc_input.batch_offsets), logits
         return point_logits(self.pc_encoder, x, self.linear)
+
+    def point_loss(self, x, y_orig, return_counts=False):
+        """The training step on pseudo labels without the per-point logits: (scene logits (B, 20), point cross
+        entropy of the logits against y_orig (N,) int64, -100 ignored), the two quantities train.py:69-74 takes
+        from `forward((x, text), istrain=True)` and `Classification`, through the encoder's voxel-level tail
+        (SparseConvBase_.point_loss).  x: the point-cloud batch (coords, feature, batch_offsets)."""
+        fn = getattr(self.pc_encoder, "point_loss", None)
+        if fn is not None:
+            return fn(x, self.linear, y_orig, return_counts=return_counts)
+        logits = self.linear(self.pc_encoder(x))
+        scene = segment_mean(logits, x.batch_offsets)
+        loss, n_kept, n_bad = point_cross_entropy(logits, y_orig, return_counts=True)
+        return (scene, loss, n_kept, n_bad) if return_counts else (scene, loss)
 
 
 @MODEL_REGISTRY.register()

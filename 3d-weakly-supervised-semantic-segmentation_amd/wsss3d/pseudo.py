@@ -109,6 +109,18 @@ def point_cross_entropy(logits, labels, return_counts=False):
     return (loss, n_kept, n_bad) if return_counts else loss
 
 
+def voxel_point_cross_entropy(x, weight, bias, labels, level, rules, n_scenes, return_counts=False):
+    """The training tail on pseudo labels (`models/MultiLabelContrastive.py:88-94` with `utils/loss.py:29-33`)
+    from the level-0 voxel rows x (V, C_in) of an encoder, before its OutputLayer: with the per-point logits
+    logits[p] = weight x[v(p)] + bias, returns (per-scene mean logits (B, C), point_cross_entropy(logits, labels))
+    without forming the (N, C) logits or their gradient (ops.VoxelCrossEntropyFunction).  level / rules: the
+    level-0 `Level` and the `InputRules` of the batch's metadata; scene b must be the points of batch id b
+    (`InputRules.scene_ranges_match`).  With return_counts also (n_kept, n_bad) as 0-dim device tensors."""
+    scene, loss, n_kept, n_bad = ops.VoxelCrossEntropyFunction.apply(x, weight, bias, labels, level, rules,
+                                                                     int(n_scenes))
+    return (scene, loss, n_kept, n_bad) if return_counts else (scene, loss)
+
+
 @LOSS_REGISTRY.register()
 def PointClassification(logits: torch.Tensor, labels: torch.Tensor):
     """The point branch of `Classification` for training on pseudo labels (train.py:73-74), capturable."""

@@ -533,6 +533,30 @@ int msp_point_ce_fwd(const float* logits, int64_t N, int C, const int64_t* label
 int msp_point_ce_bwd(const float* logits, int64_t N, int C, const int64_t* labels, const float* lse,
                      const int64_t* n_kept, const float* gout, float* dlogits, msp_stream_t stream);
 
+/* The same loss for per-point logits that are gathered voxel rows (the head's Linear on the level-0 voxel rows,
+ * models/MultiLabelContrastive.py:88-94), taken on the voxel rows themselves: no (N, C) tensor is read or written.
+ * vl: V rows of row stride ld floats (C <= ld <= 1024), z_v = vl[v][:C] + bias (bias may be NULL); the points of
+ * voxel v are perm[vstart[v] .. vstart[v+1]) (InputLayer), labels[N] is in point order.
+ * Forward: lse[v] = log sum_c exp(z_v[c]) (row maximum subtracted) once per voxel, kept[v] (int32) = its points
+ * with 0 <= label < C, loss = sum over those points of (lse[v] - z_v[label]) / n_kept in a fixed order (fp64 block
+ * partials in ws, then one block: bitwise reproducible).  loss, n_kept, n_bad as msp_point_ce_fwd writes them.
+ * ws_bytes >= msp_voxel_ce_workspace_size(V).
+ * Backward, one pass over the voxels:
+ *   dvl[v][c] = gout * (kept[v] * exp(z_v[c] - lse[v]) - hist_v[c]) / n_kept + (cnt_v / npts[b(v)]) * gscene[b(v)][c]
+ * with hist_v[c] the kept points of v labelled c (recounted from the labels), cnt_v = vstart[v+1] - vstart[v] and
+ * b(v) = keys[v] >> shift; the second term is the adjoint of the per-scene mean of the per-point logits
+ * (msp_scene_mean_bwd) and is left out when gscene ((B, C), dense) is NULL; keys / npts are then not read.
+ * Columns C .. ld-1 of dvl are written as zeros.  n_kept = 0 gives a zero first term.  gout (f32 scalar) and
+ * n_kept are read from device memory.  dvl may be vl itself (a tile's rows are read before they are written). */
+size_t msp_voxel_ce_workspace_size(int64_t V);
+int msp_voxel_ce_fwd(const float* vl, int64_t V, int64_t ld, int C, const float* bias, const int32_t* perm,
+                     const int32_t* vstart, const int64_t* labels, int64_t N, float* loss, int64_t* n_kept,
+                     int64_t* n_bad, float* lse, int32_t* kept, void* ws, size_t ws_bytes, msp_stream_t stream);
+int msp_voxel_ce_bwd(const float* vl, int64_t V, int64_t ld, int C, const float* bias, const int32_t* perm,
+                     const int32_t* vstart, const int64_t* labels, int64_t N, const float* lse, const int32_t* kept,
+                     const int64_t* n_kept, const float* gout, const float* gscene, const uint64_t* keys, int shift,
+                     int B, const int64_t* npts, float* dvl, msp_stream_t stream);
+
 /* ---------------- batch assembly on the device:
  * the per-point part of trainMerge (mode 0, dataset/data.py:135-238) and
  * valMerge (mode 1, :256-310) for B scenes already in HBM.  Scene b is points
