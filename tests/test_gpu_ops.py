@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import sparseconvnet as scn
+from conv_ref import check_local_rulebook as _check_local_rulebook
 from oracle import scn_oracle as O
 from wsss3d.synthetic import make_batch, random_cloud
 
@@ -503,11 +504,17 @@ def test_conv_tile_split_bf16_accuracy(cin, cout, flip):
     products of exact three-piece splits (msp_conv_x6.hip).  Its error against
     an fp64 evaluation must be fp32-class: at most 3x that of a plain fp32
     evaluation (torch gather + fp32 GEMM) of the same sum, and below
-    1e-6 of the output scale.  c_out <= 32 with c_in <= 64 takes the per-wave
-    form (conv_x6r_kernel: weights per offset run), the rest the tile-local form,
-    whose MFMAs accumulate the six piece products straight into the running sums
-    (one rounding per product instead of per step: 1.5-3x the fp32 evaluation's
-    error, measured 4.2e-7 / 7.0e-7 at 64->64 / 256->128)."""
+    1e-6 of the output scale.  Two calls per case, both under that bar.
+    ops.conv_tile asks conv_form: c_out <= 32 with c_in <= 64 takes the per-wave
+    form (conv_x6r_kernel: weights per offset run); 64+ channels on both sides at
+    this size (>= 4096 rows: msp_conv_local_preferred) take the tile-local form
+    (msp_conv_local, conv_x6s_kernel), so (64,64), (96,96) and (256,128) measure
+    that one; the rest take the shared tile (conv_x6d_kernel), whose MFMAs
+    accumulate the six piece products straight into the running sums (one rounding
+    per product instead of per step: 1.5-3x the fp32 evaluation's error, measured
+    4.2e-7 / 7.0e-7 at 64->64 / 256->128).  The direct msp_conv_tile call on the
+    128-row tile rulebook takes msp_conv_tile_form's form whatever conv_form
+    prefers: the shared tile for every case but the three per-wave ones."""
     from sparseconvnet import ops
     torch.manual_seed(cin + cout)
     coords, feats = _inputs(20000, 40, n_batch=2)
@@ -517,14 +524,40 @@ def test_conv_tile_split_bf16_accuracy(cin, cout, flip):
     V = lvl.n
     x = torch.randn(V, cin, device=DEV)
     wt = torch.randn(27, cout, cin, device=DEV) / (27 * cin) ** 0.5
-    y = ops.conv_tile(x, wt, 27, flip, cout, rules, V)
+    from sparseconvnet import _lib
+
+    class Kinds:
+        def __init__(self):
+            self.kinds = set()
+
+        def run(self, kind, flops, fn, nbytes=0):
+            self.kinds.add(kind.split("[")[0])
+            return fn()
+    rec = Kinds()
+    _lib.set_recorder(rec)
+    try:
+        y = ops.conv_tile(x, wt, 27, flip, cout, rules, V)
+    finally:
+        _lib.set_recorder(None)
+    narrow = cout <= 32 and cin <= 64
+    local = bool(_lib.query("msp_conv_local_preferred", _lib.I64(V), cin, cout))
+    assert V >= 4096 and local == (cin >= 64 and cout >= 64)
+    want = "x6s" if local else ("x6r" if narrow else "x6d")
+    assert rec.kinds == {"conv_tile/" + want}, (rec.kinds, want)
+    # the same sum through msp_conv_tile itself, whatever conv_form prefers: the shared tile unless narrow
+    direct = "x6r" if narrow else "x6d"
+    assert int(_lib.query("msp_conv_tile_form", _lib.I64(V), cin, cout, 128)) == (1 if narrow else 2)
+    yd = _gather_form(x, wt, flip, cout, rules, V)
     ref = _subm_ref(x, wt, rules.nbr, flip, torch.float64)
     y32 = _subm_ref(x, wt, rules.nbr, flip, torch.float32)
     scale = ref.abs().max().item()
     e_x6 = (y.double() - ref).abs().max().item() / scale
+    e_dir = (yd.double() - ref).abs().max().item() / scale
     e_f32 = (y32.double() - ref).abs().max().item() / scale
-    print(f"conv_tile {cin}->{cout} flip {flip}: max err {e_x6:.2e} (fp32 evaluation {e_f32:.2e})")
+    print(f"conv_tile {cin}->{cout} flip {flip}: max err {e_x6:.2e} ({want}), direct msp_conv_tile {e_dir:.2e} "
+          f"({direct}) (fp32 evaluation {e_f32:.2e})")
     assert e_x6 <= max(3.0 * e_f32, 1e-7) and e_x6 < 1e-6, (e_x6, e_f32)
+    assert e_dir <= max(3.0 * e_f32, 1e-7) and e_dir < 1e-6, (e_dir, e_f32)
 
 
 @pytest.mark.parametrize("cin,cout,flip", [(64, 64, 0), (64, 64, 1), (32, 64, 1), (96, 96, 0), (192, 96, 1),
@@ -895,51 +928,6 @@ def _gather_form(x, wt, flip, cout, rules, V):
               ptr(tl["chunk_off"]), ptr(tl["chunk_src"]), ptr(tl["chunk_row"]), V, ptr(out), ptr(ws), wsb,
               _lib.stream(x.device))
     return out
-
-
-def _check_local_rulebook(nbr, loc, n):
-    K = nbr.size(0)
-    T, nt = loc["tile_rows"], loc["n_tiles"]
-    us = loc["u_start"][:nt + 1].cpu()
-    u_rows = loc["u_rows"].cpu()
-    perm = loc["perm"][:nt * T].view(nt, T).cpu()
-    lidx = loc["lidx"][:, :nt * T].cpu().to(torch.int64) & 0xFFFF  # uint16 bits in an int16 tensor
-    nb = nbr.cpu()
-    assert loc["total"] == int(us[-1]) and loc["max_u"] == int((us[1:] - us[:-1]).max())
-    for t in range(nt):
-        rows = perm[t]
-        valid = rows >= 0
-        assert int(valid.sum()) == min(T, n - t * T)
-        assert bool((~valid[int(valid.sum()):]).all())  # padding last
-        assert sorted(rows[valid].tolist()) == list(range(t * T, t * T + int(valid.sum())))
-        u = u_rows[int(us[t]):int(us[t + 1])]
-        assert bool((u[1:] > u[:-1]).all())
-        ent = nb[:, rows[valid].long()]
-        assert sorted(set(ent[ent >= 0].tolist())) == u.tolist()
-        li = lidx[:, t * T:(t + 1) * T][:, :int(valid.sum())]
-        absent = ent < 0
-        assert bool((li[absent] == 0xFFFF).all())
-        assert torch.equal(u[li[~absent]], ent[~absent])
-    wo = loc.get("wave_off")
-    if T == 128 and K <= 27:  # conv_x6s's offset lists: per half, every offset some row has, once, packed
-        wo = wo[:nt * 64].view(nt, 2, 4, 8).cpu().to(torch.int64)
-        has = torch.zeros(K, nt * T, dtype=torch.bool)
-        for t in range(nt):
-            rows = perm[t]
-            has[:, t * T:t * T + int((rows >= 0).sum())] = nb[:, rows[rows >= 0].long()] >= 0
-        has = has.view(K, nt, T // 16, 16).any(3)  # [K][tile][group]
-        for t in range(nt):
-            for h in range(2):
-                need = sorted(o for o in range(K) if bool(has[o, t, h::2].any()))
-                lists = wo[t, h]
-                got = []
-                for c in range(4):
-                    n = int((lists[c] != 0xFF).sum())
-                    assert bool((lists[c, :n] != 0xFF).all()) and bool((lists[c, n:] == 0xFF).all())
-                    got += lists[c, :n].tolist()
-                assert sorted(got) == need, (t, h)
-    else:
-        assert wo is None
 
 
 def test_tile_local_rulebook():
